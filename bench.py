@@ -11,6 +11,13 @@ Random-init weights.  bf16 MFMA compute, fp32 master weights / statistics.
     python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1: starts N ranks itself)
     torchrun --nproc-per-node N bench.py --gpus N ...        (or one rank per GPU via torchrun)
 
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what
+takes runs of its own after the timed region: the per-family event probe (`roofline`), the parity
+check against the CPU oracle (`parity`) and the CPU baseline (`cpu_baseline`); without it those
+three fields are null.  `--dump-outputs DIR` writes what the last timed step computed (loss, V / A
+predictions, the parameters after its SGD update) as DIR/<name>.npy, float32; the inputs and the
+initial weights are seeded, so two builds can be compared output for output.
+
 One process per GPU either way (RCCL).  The reference scales to every visible GPU by itself
 (main.py:487-491 wraps the model in DataParallel, tools.py:16-21); `--gpus N` without torchrun's
 environment makes this script the launcher: it starts N worker processes of itself before any
@@ -353,6 +360,33 @@ def cpu_baseline(model_sd, fc_sd, audio, video, lv, la, steps=2):
                               "shared with the other GPU slots, so it is not used"}
 
 
+DUMP_PARAM_SAMPLE = 4 << 20     # elements of the parameter vector kept by --dump-outputs (16 MiB)
+
+
+def dump_outputs(path: str, loss, preds: dict, model, fc):
+    """--dump-outputs: what a caller of the timed step has after its last call, as float32
+    <name>.npy files under `path` (rank 0's share for N > 1): `loss` (the step's return value),
+    `v_pred` / `a_pred` (the model outputs that loss was computed from) and `params`, the fp32
+    master parameters after the step's SGD update, flattened in state order (the model's
+    parameters(), then the FcLayer's).  A parameter vector longer than DUMP_PARAM_SAMPLE is
+    written as a fixed sample of that many elements (positions drawn once with seed 0, sorted), so
+    the files stay well under 64 MB in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    out = {"loss": loss.detach().float().reshape(1)}
+    out.update({k: v.float() for k, v in preds.items()})
+    ps = list(model.parameters()) + (list(fc.parameters()) if fc is not None else [])
+    flat_p = torch.cat([p.detach().float().reshape(-1) for p in ps])
+    if flat_p.numel() > DUMP_PARAM_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(flat_p.numel(), DUMP_PARAM_SAMPLE,
+                                                      replace=False))
+        flat_p = flat_p[torch.from_numpy(idx).to(flat_p.device)]
+    out["params"] = flat_p
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def visible_gpus():
     """GPUs this process may use, WITHOUT initialising HIP (the launcher parent must not touch the
     GPU before it starts its ranks): the first of HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES /
@@ -524,6 +558,14 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="windows per GPU (config default)")
     ap.add_argument("--seq", type=int, default=None, help="T (config default)")
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-family event probe (roofline), "
+                         "the parity check against the CPU oracle and the CPU baseline (each can "
+                         "still be switched off by its --no-* option); a plain run times the steps "
+                         "and reports those fields as null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss, v_pred, a_pred, params) "
+                         "as DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--parity-perturb", type=float, default=0.0,
@@ -555,6 +597,8 @@ def main():
         jcfg = jconfig.override(jconfig.load(args.config_file), extra)
     elif extra:
         ap.error(f"unrecognized arguments: {' '.join(extra)}")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ:
         if (args.gpus or 1) > 1:
@@ -623,10 +667,11 @@ def main():
     model = Two_transformers(drop[0], drop[1], heads, layers, cfg["jm"], cfg["fmt"], Dv,
                              digitize_num=k).to(dev)
     fc = FcLayer(Da, E).to(dev) if cfg["fc"] else None
+    # the initial weights, for --full's CPU baseline
     model_sd0 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} \
-        if rank == 0 else None
+        if rank == 0 and args.full else None
     fc_sd0 = {k: v.detach().cpu().clone() for k, v in fc.state_dict().items()} \
-        if rank == 0 and fc is not None else None
+        if rank == 0 and args.full and fc is not None else None
     if world > 1:
         jdist.set_loss_group(dist.group.WORLD)
 
@@ -645,9 +690,15 @@ def main():
     # (CCCLoss.forward_add), backward seeded with a persistent 1 — the step runs no torch kernel
     one = torch.ones((), dtype=torch.float32, device=dev)
 
+    # --dump-outputs: the predictions of the latest step (detached: no autograd graph is kept;
+    # under graph replay these are the capture's static output tensors)
+    preds = {}
+
     def fwd_bwd():
         with JF.compute_mode(cd):
             vo, ao = model(fc(audio) if fc is not None else audio, video)
+            if args.dump_outputs:
+                preds["v_pred"], preds["a_pred"] = vo.detach(), ao.detach()
             l1 = crit(flat(vo), lv)
             loss = crit.forward_add(flat(ao), la, l1)
             if scaler is not None:
@@ -735,7 +786,10 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     last_loss = float(loss.detach())
-    if not args.no_probe:
+    if args.dump_outputs and rank == 0:
+        # before anything else steps the model: the probe steps below train on
+        dump_outputs(args.dump_outputs, loss, preds, model, fc)
+    if args.full and not args.no_probe:
         # per-launch HIP events cannot sit inside the replayed graph (and would add host work to
         # an eager timed region): the dominant kernel is timed over `probe_steps` eager steps
         # right after the timed region, on the stream its launches go to.  The weight-gradient
@@ -824,13 +878,15 @@ def main():
               f"final loss {last_loss:.6f}", file=sys.stderr, flush=True)
     # the parity and CPU legs run on rank 0 alone: the CCC losses inside them must use local
     # statistics (a loss group would all-gather with ranks that are not there)
-    group = jdist.loss_group()
-    jdist.set_loss_group(None)
-    try:
-        parity, cpu = _rank0_legs(args, cfg, cd, k, heads, layers, B, T, Da, Dv, model, fc, audio,
-                                  video, lv, la, rank, world, jcfg, model_sd0, fc_sd0)
-    finally:
-        jdist.set_loss_group(group)
+    parity, cpu = None, None
+    if args.full:
+        group = jdist.loss_group()
+        jdist.set_loss_group(None)
+        try:
+            parity, cpu = _rank0_legs(args, cfg, cd, k, heads, layers, B, T, Da, Dv, model, fc,
+                                      audio, video, lv, la, rank, world, jcfg, model_sd0, fc_sd0)
+        finally:
+            jdist.set_loss_group(group)
     if rank == 0:
         out = {
             "metric": "train windows/sec + CCC parity, B=64 T=300 A/V fusion, 1/2/4/8 MI355X",

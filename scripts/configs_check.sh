@@ -9,7 +9,7 @@ timeout -k 5 200 python -u -m pytest tests/test_gpu_realdata.py -x -q --timeout 
 rc=$?; echo "realdata tests exit $rc"; tail -1 $OUT/${TAG}_realdata.log
 if [ $rc -gt 1 ]; then exit $rc; fi
 for c in ${CONFIGS:-realdata c2 c4 c5 c3sa}; do
-  timeout -k 10 300 python bench.py --config $c --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline > $OUT/${TAG}_$c.log 2>&1
+  timeout -k 10 300 python bench.py --full --config $c --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline > $OUT/${TAG}_$c.log 2>&1
   r=$?
   if [ $r -ne 0 ]; then echo "$c exit $r"; tail -12 $OUT/${TAG}_$c.log; exit $r; fi
   tail -1 $OUT/${TAG}_$c.log | python3 -c "

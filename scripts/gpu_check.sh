@@ -14,7 +14,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TA
 rc=$?
 echo "smoke exit $rc"; tail -3 $OUT/${TAG}_smoke.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 400 python bench.py --steps ${STEPS:-10} --warmup 3 ${BENCH_ARGS:-} > $OUT/${TAG}_bench.log 2>&1
+timeout -k 10 400 python bench.py --full --steps ${STEPS:-10} --warmup 3 ${BENCH_ARGS:-} > $OUT/${TAG}_bench.log 2>&1
 rc=$?
 echo "bench exit $rc"; tail -5 $OUT/${TAG}_bench.log
 exit $rc

@@ -7,7 +7,7 @@ JMT_CAPTURE_STREAMS=${JMT_CAPTURE_STREAMS:-1} timeout -k 10 300 python -u -m pyt
 rc=$?; echo "graph tests exit $rc"; tail -6 $OUT/${TAG}_graph_tests.log
 if [ $rc -gt 1 ]; then exit $rc; fi
 for mode in "--graph" "--no-graph"; do
-  JMT_CAPTURE_STREAMS=${JMT_CAPTURE_STREAMS:-1} timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline $mode > $OUT/${TAG}_bench${mode}.log 2>&1
+  JMT_CAPTURE_STREAMS=${JMT_CAPTURE_STREAMS:-1} timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $mode > $OUT/${TAG}_bench${mode}.log 2>&1
   rc=$?; echo "bench $mode exit $rc"; grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*\|"host_issue_ms_per_eager_step": [0-9.]*\|"frac": [0-9.]*' $OUT/${TAG}_bench${mode}.log | tr '\n' ' '; echo
   if [ $rc -ne 0 ]; then tail -20 $OUT/${TAG}_bench${mode}.log; exit $rc; fi
 done

@@ -8,7 +8,7 @@ rc=$?; echo "tests exit $rc"; tail -25 $OUT/${TAG}_tests.log | grep -v "^  " | t
 if [ $rc -gt 1 ]; then exit $rc; fi
 run() {  # name, env..., args
   local name=$1; shift
-  env "$@" JMT_CAPTURE_STREAMS=0 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_EXTRA:-} > $OUT/${TAG}_$name.log 2>&1
+  env "$@" JMT_CAPTURE_STREAMS=0 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_EXTRA:-} > $OUT/${TAG}_$name.log 2>&1
   local r=$?; echo "bench $name exit $r: $(grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*\|"host_issue_ms_per_eager_step": [0-9.]*\|"frac": [0-9.]*' $OUT/${TAG}_$name.log | tr '\n' ' ')"
   if [ $r -ne 0 ]; then tail -20 $OUT/${TAG}_$name.log; fi
   return $r

@@ -7,6 +7,6 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- \
-    python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_stdout.log 2>&1
+    python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_stdout.log 2>&1
 rc=$?; echo "rocprof exit $rc"; tail -1 $OUT/bench_stdout.log | grep -o '"avg_launch_us": [0-9.]*'
 exit $rc

@@ -10,7 +10,7 @@ OUT=gpurun_out/r06/ev_$C
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format rocpd csv -d $OUT/prof -o run -- \
-    python3 bench.py --steps 200 --warmup 10 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1 \
+    python3 bench.py --full --steps 200 --warmup 10 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1 \
     || { echo "rocprof bench failed"; tail -20 $OUT/bench_under_rocprof.log; exit 1; }
 db=$(find $OUT/prof -name "*results.db" | head -1)
 stats=$(find $OUT/prof -name "*kernel_stats.csv" | head -1)

@@ -7,5 +7,5 @@ JMT_GEMM_CFG=6 timeout -k 10 200 python -m pytest tests/test_gpu_kernels.py -q -
 rc=$?; echo "cfg 6 tests: $(tail -1 $OUT/kcfg6.log)"
 if [ $rc -gt 1 ]; then exit $rc; fi
 timeout -k 10 300 python scripts/bench_gemm_step.py --cfg 0 1 6 > $OUT/sched_step2.log 2>&1 || exit $?
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_prio.log 2>&1 || exit $?
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_prio.log 2>&1 || exit $?
 tail -1 $OUT/bench_prio.log

@@ -145,7 +145,7 @@ def test_bench_gpus2_on_cpu_box_launches_two_ranks_and_fails_loudly():
 def test_bench_gpus2_gloo_on_one_gpu():
     """`python bench.py --gpus 2` (no torchrun): two gloo ranks on cuda:0 run the eager bucketed
     step, rank 0 relays n_gpus 2 with parity passing, both ranks log."""
-    r = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4",
+    r = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--full",
                     "--probe-steps", "1", "--no-cpu-baseline"],
                    {"JMT_DIST_BACKEND": "gloo"}, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
