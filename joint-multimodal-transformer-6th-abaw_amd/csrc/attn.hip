@@ -8,8 +8,13 @@
 // reference (F.multi_head_attention_forward, called from mm_multi_transformers.py:57,142-167,
 // 191 and intra_modal_transformer_fusion.py) and its autograd backward.
 //
-// Geometry (both kernels): a block is 8 waves (512 threads, 2 waves per SIMD at one block per
-// CU) owning 64 rows of the row operand (Q forward, Q / dO backward).  Wave w owns rows
+// Two geometries.  Whole rows (round 6 backward attn_bwd_pds_kernel, round 7 forward
+// attn_fwd_rows_kernel; their own headers below): a block is 8 waves x 16 rows = 128 rows, a wave
+// contracts all 512 head dims itself, 32-key tiles double-buffered, one barrier per tile, 128 KiB
+// of LDS.  jmt_attn_fwd takes it for Lq > 64 (JMT_ATTN_FWD_ROWS=0: never); Lq <= 64 stays on the
+// 64-row kernel, whose arithmetic attn_short.hip reproduces bit for bit.
+// Half rows (attn_fwd_kernel, attn_bwd_kernel): a block is 8 waves (512 threads, 2 waves per SIMD
+// at one block per CU) owning 64 rows of the row operand (Q forward, Q / dO backward).  Wave w owns rows
 // 16 (w & 3) .. +15 and HALF h = w >> 2 of the 512 head dims: its row-operand fragments
 // (16 rows x 256 dims) and its accumulator (O or dQ: 16 rows x 256 dims, 64 registers) stay in
 // registers.  The contraction over head dims of the score products (Q K^T, dO V^T) is split
@@ -851,15 +856,283 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(AttnBwdArgs p) {
   }
 }
 
+// ------------------------------------------------------------------ forward, whole rows (round 7)
+// The forward in the geometry of attn_bwd_pds_kernel: a block is 8 waves x 16 rows = 128 query
+// rows, wave w owns rows q0 + 16 w .. +15 over all 512 head dims (Q: 16 fragments, 64 VGPRs; the
+// fp32 O accumulator: 32 sub-tiles, 128 VGPRs).  Against attn_fwd_kernel:
+//  * no exchange: a wave contracts all 512 dims of its scores itself, so no partial-score slots,
+//    no pair barrier and no pair-synchronised softmax — ONE barrier per key tile (the K / V
+//    buffer turnover), preceded by the vmcnt that retires the next tile's DMA;
+//  * every K / V tile staged into LDS feeds 128 rows (64): half the L2 -> LDS fill per row;
+//  * 32-key tiles, K and V double-buffered (tile j+1's DMA issued at the start of tile j, P/dS
+//    kernel's stage_tile: inline-asm LDS-DMA, 32-bit row offsets, lane offsets computed once);
+//  * waves whose 16 rows all lie past Lq skip their MFMAs, softmax and stores (wave-uniform).
+// The scores keep attn_fwd_kernel's summation order: dims 0-255 and 256-511 in separate MFMA
+// chains, added lo + hi (bitwise the scores of the 64-row kernel; the four independent chains
+// also cover the MFMA dependency latency).  Online softmax with lazy rescaling as there, per
+// 32-key tile.  Per tile a wave reads the K and V tiles whole (64 KiB) and issues 64 MFMAs: LDS
+// array and MFMA pipes both at 2048 cycles per tile at 2 waves per SIMD.
+// LDS: 2 x (K 32 KiB + V 32 KiB) = 128 KiB; 252 VGPRs, no spill, no scratch (both dtypes).
+// Tried and dropped: 4-fragment score batches and per-lane 64-bit DMA
+// addresses (spilled Q); 2-fragment P V batches (same time); leaving an item's O stores in flight
+// across the next item's start (Q loads from inline asm, counted wait: same time).  Ablations
+// (profiles/r07/fwd_rows_ablate.txt): the K / V fill and the O stores alone take 131 of the
+// 150-158 us of the c3 cross-attention launch — the kernel is bound by the L2 -> LDS fill with
+// one 64 KiB tile in flight per CU, not by its MFMAs or LDS reads.
+constexpr int AR_QT = 128;
+constexpr int AR_KT = 32;
+constexpr int AR_LDS = 4 * AR_KT * AT_ROWB;
+constexpr int AR_VB = 4;             // V fragments per P V read batch
+
+// DBG (ablations, timing only, wrong results; JMT_ATTN_FWD_ROWS_DBG in the diagnostic build):
+// 2 no score reads / MFMAs, 4 no softmax, 8 no K / V DMA after an item's tile 0, 16 no P V reads /
+// MFMAs, 32 no O / lse stores.
+template <typename T, int DBG = 0>
+__global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
+  typedef typename Frag16<T>::t F;
+  typedef typename Frag16<T>::h Hf;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int IMG = AR_KT * AT_ROWB;            // one K or V image (32 KiB)
+
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int g = lane >> 4, li = lane & 15;
+  const int nqt = (p.Lq + AR_QT - 1) / AR_QT;
+  const int nkt = (p.Lk + AR_KT - 1) / AR_KT;
+  int item, iend, istride;
+  item_range(p.nitems, item, iend, istride);
+  if (item >= iend) return;
+
+  int nh = item / nqt, n = nh / p.H, hd = nh % p.H, q0 = (item % nqt) * AR_QT;
+  const T* kb = (const T*)p.k + (int64_t)n * p.sk_n + hd * AT_DH;
+  const T* vb = (const T*)p.v + (int64_t)n * p.sv_n + hd * AT_DH;
+
+  // lane (li, g): row q0 + 16 w + li, dims 32 ks + 8 g .. +7 of fragment ks
+  F qf[16];
+  auto load_q = [&](int n_, int hd_, int q0_) {
+    const T* qrow = (const T*)p.q + (int64_t)n_ * p.sq_n + hd_ * AT_DH +
+                    (int64_t)min(q0_ + 16 * w + li, p.Lq - 1) * p.sq_l + 8 * g;
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) qf[ks] = *(const F*)(qrow + 32 * ks);
+  };
+  load_q(n, hd, q0);
+  int buf = 0;
+  // K / V tile staging as attn_bwd_pds_kernel: wave w stages rows 4 w .. +3 of both images, row
+  // offsets in 32-bit byte arithmetic from the (n, h) base (the host checks Lk rows fit)
+  const int wu = __builtin_amdgcn_readfirstlane(w);
+  const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  unsigned loff[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) loff[i] = (unsigned)(lane ^ (((4 * wu + i) & 7) << 1)) << 4;
+  const int ldk = (int)(p.sk_l * (int64_t)sizeof(T)), ldv = (int)(p.sv_l * (int64_t)sizeof(T));
+  auto stage_tile = [&](int b, const T* kbase, const T* vbase, int k0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 4 * wu + i;
+      const int src = min(k0 + r, p.Lk - 1);
+      JMT_DCHECK(src >= 0 && src < p.Lk);
+      const uint32_t dst = lbase + b * 2 * IMG + r * AT_ROWB;
+      glds16_sv((const char*)kbase + (unsigned)(src * ldk), loff[i], dst);
+      glds16_sv((const char*)vbase + (unsigned)(src * ldv), loff[i], dst + IMG);
+    }
+  };
+  stage_tile(0, kb, vb, 0);
+  // Lane bases of the fragment reads: row_base(m) = row_base(0) ^ (m << 6) and tr_base(c) =
+  // tr_base(0) ^ (c << 5) (the swizzle XOR and m / c sit in the same chunk bits), formed by one
+  // VALU XOR in front of the reads that use them instead of living in 12 registers over the
+  // whole kernel (the O accumulator and Q leave 64 for everything else); asm volatile keeps
+  // hipcc from hoisting them back out of the tile loop.
+  const int kb0 = row_base(0, li, g, 0), tb0 = tr_base(0, li, g, 0);
+  auto lane_base = [](int base, int bits) __attribute__((always_inline)) {
+#if !defined(__OPTIMIZE__)
+    return base ^ bits;
+#else
+    int r;
+    asm volatile("v_xor_b32 %0, %2, %1" : "=v"(r) : "v"(base), "i"(bits));
+    return r;
+#endif
+  };
+
+  while (true) {
+    const int qr = q0 + 16 * w + li;
+    // wave-uniform (scalar branches, not EXEC masks): any row of this wave in range
+    const bool wact = __builtin_amdgcn_readfirstlane(q0 + 16 * w) < p.Lq;
+    const int nxt = item + istride;
+    const bool more = nxt < iend;
+    const int nh2 = nxt / nqt, n2 = nh2 / p.H, hd2 = nh2 % p.H, q02 = (nxt % nqt) * AR_QT;
+    const T* kb2 = (const T*)p.k + (int64_t)n2 * p.sk_n + hd2 * AT_DH;
+    const T* vb2 = (const T*)p.v + (int64_t)n2 * p.sv_n + hd2 * AT_DH;
+
+    f32x4 o[32];
+#pragma unroll
+    for (int t = 0; t < 32; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+
+    wait_vmcnt<0>();                              // tile 0 and this item's Q landed (and the
+                                                  // previous item's O stores left)
+    // a use of Q here: hipcc's own wait for the Q loads goes in front of it, outside the tile
+    // loop (inside, it would drain each tile's freshly issued DMA before the first MFMA)
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) asm volatile("" : "+v"(qf[ks]));
+    lds_barrier();                                // ... for every wave; the previous item's
+                                                  // buffers are free
+    // One 32-key tile; the last one (LAST) is peeled out of the loop so that the next item's Q
+    // loads are not pending at the loop header (attn_bwd_pds_kernel).
+    auto tile = [&](int j, auto last_c) {
+      constexpr bool LAST = decltype(last_c)::value;
+      const char* kimg = smem + buf * 2 * IMG;
+      const char* vimg = kimg + IMG;
+      if ((!LAST && (DBG & 8) == 0) || (LAST && more))
+        stage_tile(buf ^ 1, LAST ? kb2 : kb, LAST ? vb2 : vb, LAST ? 0 : AR_KT * (j + 1));
+      // ---- scores <row qr, key 32 j + 16 kt + 4 g + r>: dims 0-255 into sl, 256-511 into sh
+      f32x4 sl[2], sh[2];
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+        sl[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        sh[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      if ((DBG & 2) == 0 && wact) {   // batches of 2 K fragments (key subtiles 0, 1 of one k-step, dims 0-255 and
+                    // 256-511 alternating), double-buffered: the next batch is in flight while
+                    // the 2 MFMAs of this one run (4-fragment batches spill Q)
+        F fa[2], fb[2];
+        auto batch = [&](F* dst, const char* a) {
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt) dst[kt] = *(const F*)(a + 16384 * kt);
+        };
+        const char* a = kimg + lane_base(kb0, 0);
+        batch(fa, a);
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+          batch(fb, a + 512);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt) sl[kt] = mfma16(fa[kt], qf[ks], sl[kt]);
+          __builtin_amdgcn_sched_barrier(0);
+          if (ks + 1 < 8) {
+            a = kimg + lane_base(kb0, ((ks + 1) & 3) << 6) + 256 * ((ks + 1) >> 2);
+            batch(fa, a);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt) sh[kt] = mfma16(fb[kt], qf[ks + 8], sh[kt]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if constexpr (LAST) {
+        if (more) load_q(n2, hd2, q02);           // registers free after the score MFMAs
+      }
+      if (wact) {
+        F pf;
+        if constexpr ((DBG & 4) != 0) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) pf[e] = from_f<T>(0.f);
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt)
+            asm volatile("" ::"v"(sl[kt][0]), "v"(sl[kt][3]), "v"(sh[kt][0]), "v"(sh[kt][3]));
+        } else {
+        // ---- online softmax of the tile (lazy rescale: attn_fwd_kernel)
+        const int kbase = AR_KT * j + 4 * g;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+          const f32x4 full = sl[kt] + sh[kt];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float x = (kbase + 16 * kt + r < p.Lk) ? full[r] * p.scale_log2 : -INFINITY;
+            sl[kt][r] = x;
+            mx = fmaxf(mx, x);
+          }
+        }
+        mx = pl_pair_max(mx);
+        if (__any(mx > m_run + 8.f)) {
+          const float m_new = fmaxf(m_run, mx);
+          const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+          m_run = m_new;
+          l_run *= alpha;
+#pragma unroll
+          for (int t = 0; t < 32; ++t) o[t] *= alpha;
+        }
+        float ls = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float pv = __builtin_amdgcn_exp2f(sl[kt][r] - m_run);
+            ls += pv;
+            pf[kt * 4 + r] = from_f<T>(pv);
+          }
+        l_run += ls;
+        }
+        if constexpr ((DBG & 16) != 0) {
+          asm volatile("" ::"v"(pf));
+        } else {
+        // ---- o[t] += sum_k P(k) V[k][16 t + 4 g + r]: transposed fragment reads of the V image
+        // in double-buffered batches of NB fragments
+        constexpr int NB = AR_VB;
+        F fa[NB], fb[NB];
+        auto vbatch = [&](F* dst, int b) {
+#pragma unroll
+          for (int i = 0; i < NB; ++i) {
+            const int t = NB * b + i;
+            const char* a = vimg + lane_base(tb0, (t & 7) << 5) + 256 * (t >> 3);
+            const Hf lo = tr_read<Hf>(a);
+            const Hf hi = tr_read<Hf>(a + 16384);
+            dst[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+          }
+        };
+        vbatch(fa, 0);
+#pragma unroll
+        for (int b = 0; b < 32 / NB; b += 2) {
+          vbatch(fb, b + 1);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < NB; ++i) o[NB * b + i] = mfma16(fa[i], pf, o[NB * b + i]);
+          __builtin_amdgcn_sched_barrier(0);
+          if (b + 2 < 32 / NB) vbatch(fa, b + 2);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < NB; ++i)
+            o[NB * (b + 1) + i] = mfma16(fb[i], pf, o[NB * (b + 1) + i]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        }
+      }
+      if constexpr (!LAST) {
+        wait_vmcnt<0>();                          // tile j+1 landed
+        lds_barrier();                            // visible to every wave; buffer `buf` free
+      }
+      buf ^= 1;
+    };
+    for (int j = 0; j + 1 < nkt; ++j) tile(j, std::false_type{});
+    tile(nkt - 1, std::true_type{});
+    if constexpr ((DBG & 32) != 0) {
+#pragma unroll
+      for (int t = 0; t < 32; ++t) asm volatile("" ::"v"(o[t]));
+      asm volatile("" ::"v"(l_run), "v"(m_run));
+    } else if (wact) {
+      const float lt = pl_pair_sum(l_run);
+      JMT_DCHECK(item < p.nitems && n * p.H + hd == nh);
+      if (qr < p.Lq && g == 0 && p.lse)
+        p.lse[(int64_t)nh * p.Lq + qr] =
+            (m_run + __builtin_amdgcn_logf(lt)) * 0.69314718055994531f;
+      T* orow = (T*)p.o + (int64_t)n * p.so_n + hd * AT_DH + (int64_t)qr * p.so_l;
+      store_acc_direct<T>(o, 1.f / lt, orow, qr < p.Lq);
+      store_acc_direct<T>(o + 16, 1.f / lt, orow + 256, qr < p.Lq);
+    }
+    if (!more) break;
+    item = nxt; nh = nh2; n = n2; hd = hd2; q0 = q02; kb = kb2; vb = vb2;
+  }
+}
+
 template <typename K>
 static void set_lds(K fn, int bytes) {
   (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-static int check_common(const char* name, int N, int H, int Lq, int Lk, const void* const* ptrs,
-                        int nptr, const int64_t* strides, int nstr) {
+// qt: query rows per item of the kernel the caller launches (the item count must fit an int)
+static int check_common(const char* name, int N, int H, int Lq, int Lk, int qt,
+                        const void* const* ptrs, int nptr, const int64_t* strides, int nstr) {
   JMT_CHECK_ARG(N > 0 && H > 0 && Lq > 0 && Lk > 0 &&
-                    (int64_t)N * H * ((Lq + AT_QT - 1) / AT_QT) < (1LL << 31),
+                    (int64_t)N * H * ((Lq + qt - 1) / qt) < (1LL << 31),
                 "%s: bad sizes", name);
   for (int i = 0; i < nptr; ++i)
     JMT_CHECK_ARG(ptrs[i] != nullptr && ((uintptr_t)ptrs[i] & 15) == 0,
@@ -926,6 +1199,23 @@ extern "C" int jmt_attn_set_stamps(void* buf) {
 #endif
 }
 
+// dev A/B switch of the forward: JMT_ATTN_FWD_ROWS=0 (read once) keeps every shape on the 64-row
+// attn_fwd_kernel; jmt_attn_set_fwd_rows(0 / 1) overrides it in-process (tests and benchmarks
+// that compare the two kernels), -1 returns to the environment's choice.  Not part of
+// include/jmt.h (dev tool, as jmt_attn_set_stamps).
+static int g_fwd_rows = -1;
+static bool fwd_rows_on() {
+  static const bool env_on = [] {
+    const char* e = getenv("JMT_ATTN_FWD_ROWS");
+    return !(e && e[0] == '0');
+  }();
+  return g_fwd_rows < 0 ? env_on : g_fwd_rows != 0;
+}
+extern "C" int jmt_attn_set_fwd_rows(int on) {
+  g_fwd_rows = on < 0 ? -1 : (on != 0);
+  return JMT_OK;
+}
+
 extern "C" int jmt_attn_supported(int dt, int dh) {
   return (dt == JMT_BF16 || dt == JMT_F16) && dh == AT_DH;
 }
@@ -940,7 +1230,13 @@ extern "C" int jmt_attn_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
                      dt, dh);
   const void* ptrs[] = {q, k, v, o};
   const int64_t strides[] = {sq_l, sq_n, sk_l, sk_n, sv_l, sv_n, so_l, so_n};
-  int rc = check_common("jmt_attn_fwd", N, H, Lq, Lk, ptrs, 4, strides, 8);
+  // The whole-row kernel (128-row items) takes Lq > 64 when its 32-bit K / V row offsets fit;
+  // Lq <= 64 stays on the 64-row kernel, whose arithmetic jmt_attn_short_fwd reproduces bit for
+  // bit (include/jmt.h).
+  const bool rows = fwd_rows_on() && Lq > AT_QT && (int64_t)Lk * sk_l * 2 < (1LL << 31) &&
+                    (int64_t)Lk * sv_l * 2 < (1LL << 31);
+  const int qt = rows ? AR_QT : AT_QT;
+  int rc = check_common("jmt_attn_fwd", N, H, Lq, Lk, qt, ptrs, 4, strides, 8);
   if (rc != JMT_OK) return rc;
   AttnFwdArgs a = {};
   a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
@@ -949,8 +1245,43 @@ extern "C" int jmt_attn_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
   a.Lq = Lq; a.Lk = Lk; a.H = H;
   a.scale_log2 = scale * 1.4426950408889634f;
   hipStream_t st = as_stream(stream);
-  a.nitems = ((Lq + AT_QT - 1) / AT_QT) * N * H;
+  a.nitems = ((Lq + qt - 1) / qt) * N * H;
   const dim3 grid(persistent_grid(a.nitems));
+  if (rows) {
+#if JMT_DIAG
+    static const int dbg =
+        getenv("JMT_ATTN_FWD_ROWS_DBG") ? atoi(getenv("JMT_ATTN_FWD_ROWS_DBG")) : 0;
+    if (dbg && dt == JMT_BF16) {
+#define JMT_ROWS_DBG(D)                                                                      \
+  case D: {                                                                                  \
+    static bool once = (set_lds(attn_fwd_rows_kernel<__bf16, D>, AR_LDS), true);             \
+    (void)once;                                                                              \
+    hipLaunchKernelGGL((attn_fwd_rows_kernel<__bf16, D>), grid, dim3(512), (size_t)AR_LDS,  \
+                       st, a);                                                               \
+  } break;
+      switch (dbg) {
+        JMT_ROWS_DBG(2) JMT_ROWS_DBG(4) JMT_ROWS_DBG(8) JMT_ROWS_DBG(16) JMT_ROWS_DBG(32)
+        JMT_ROWS_DBG(18) JMT_ROWS_DBG(22) JMT_ROWS_DBG(54) JMT_ROWS_DBG(62)
+        default: return set_error(JMT_ERR_ARG, "JMT_ATTN_FWD_ROWS_DBG=%d not built", dbg);
+      }
+#undef JMT_ROWS_DBG
+      JMT_LAUNCH_CHECK("jmt_attn_fwd");
+      return JMT_OK;
+    }
+#endif
+    if (dt == JMT_BF16) {
+      static bool once = (set_lds(attn_fwd_rows_kernel<__bf16>, AR_LDS), true);
+      (void)once;
+      hipLaunchKernelGGL((attn_fwd_rows_kernel<__bf16>), grid, dim3(512), (size_t)AR_LDS, st, a);
+    } else {
+      static bool once = (set_lds(attn_fwd_rows_kernel<_Float16>, AR_LDS), true);
+      (void)once;
+      hipLaunchKernelGGL((attn_fwd_rows_kernel<_Float16>), grid, dim3(512), (size_t)AR_LDS, st,
+                         a);
+    }
+    JMT_LAUNCH_CHECK("jmt_attn_fwd");
+    return JMT_OK;
+  }
 #if JMT_DIAG
   if (g_stamps && dt == JMT_BF16) {   // diagnostic: phase stamps (jmt_attn_set_stamps)
     a.stamps = (uint64_t*)g_stamps;
@@ -989,7 +1320,8 @@ extern "C" int jmt_attn_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
   const int64_t strides[] = {sgo_l, sgo_n, so_l, so_n, sq_l, sq_n, sk_l, sk_n, sv_l, sv_n, ldp,
                              sdq_l, sdq_n};
   const bool pds = dq == nullptr;                 // P / dS only: dQ left to jmt_attn_dkdv
-  int rc = check_common("jmt_attn_bwd", N, H, Lq, Lk, ptrs, pds ? 7 : 8, strides, pds ? 11 : 13);
+  int rc = check_common("jmt_attn_bwd", N, H, Lq, Lk, pds ? AP_QT : AT_QT, ptrs, pds ? 7 : 8,
+                        strides, pds ? 11 : 13);
   if (rc != JMT_OK) return rc;
   JMT_CHECK_ARG(lse && ldp >= Lk, "jmt_attn_bwd: lse missing or ldp < Lk");
   if (pds) {

@@ -203,6 +203,24 @@ __device__ __forceinline__ void glds16_at(const void* src, uint32_t lds_addr) {
 #endif
 }
 
+// glds16_at with the source as a wave-uniform 64-bit base (SGPR pair) + a 32-bit per-lane byte
+// offset (the saddr form): no 64-bit per-lane address per DMA in VGPRs
+__device__ __forceinline__ void glds16_sv(const void* sbase, uint32_t voff, uint32_t lds_addr) {
+#if !defined(__OPTIMIZE__)
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) void*)((const char*)sbase + voff),
+      (__attribute__((address_space(3))) void*)(uintptr_t)lds_addr, 16, 0, 0);
+#else
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds_addr)
+      : "memory");
+#endif
+}
+
 // The same instruction from the builtin: hipcc counts it in its own s_waitcnt bookkeeping (and
 // drains it before transposed LDS reads, above).  The attention kernels load their row operands
 // (Q, dO) into registers with plain loads that hipcc waits for by counting the VMEM operations

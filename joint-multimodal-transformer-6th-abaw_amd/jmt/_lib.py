@@ -85,6 +85,9 @@ _PROTOS = {
     "jmt_attn_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp,
                              c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_f, c_vp,
                              c_vp]),
+    # dev switch outside include/jmt.h: 0 / 1 force the 64-row / whole-row forward kernel, -1
+    # returns to JMT_ATTN_FWD_ROWS (csrc/attn.hip)
+    "jmt_attn_set_fwd_rows": (c_int, [c_int]),
     "jmt_attn_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp,
                              c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                              c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_f, c_vp]),

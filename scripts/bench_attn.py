@@ -2,7 +2,11 @@
 64 windows = 384 sequences, L = 300, head_dim 512, bf16) and the c4 long window (N = 6 x 16,
 L = 1024): jmt_attn_fwd and jmt_attn_bwd launched back to back, HIP events on the launch stream.
 Algorithmic FLOP: fwd 4 N L^2 d; bwd (P recompute, dP, dQ) 6 N L^2 d.
-    python scripts/bench_attn.py [N L reps]"""
+    python scripts/bench_attn.py [N L reps]
+    python scripts/bench_attn.py fwd-ab [rounds]   the forward alone at the c3 step's two
+        launches (N = 384 cross-attention, N = 192 encoders, L = 300) and c4's (N = 96,
+        L = 1024), the whole-row kernel (jmt_attn_set_fwd_rows 1) against the 64-row kernel (0),
+        the two settings interleaved round by round; medians and ranges per setting"""
 import json
 import math
 import os
@@ -63,8 +67,48 @@ def run(N, L, reps, alias=False):
     print(json.dumps(r), flush=True)
 
 
+def fwd_ab(rounds=7, reps=20):
+    """Forward A/B in one process: per shape, `rounds` rounds of (64-row, whole-row) timings."""
+    import statistics
+    from jmt import _lib
+    lib = _lib.load()
+    E = 512
+    cd = torch.bfloat16
+    dt = ops.dt(cd)
+    scale = 1.0 / math.sqrt(E)
+    for N, L in ((384, 300), (192, 300), (96, 1024)):
+        g = torch.Generator(device="cuda").manual_seed(0)
+        qkv = torch.randn(N, L, 3 * E, device="cuda", generator=g).to(cd).permute(1, 0, 2)
+        q, k, v = qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:]
+        st = (qkv.stride(0), qkv.stride(1))
+        o = torch.empty(N, L, E, device="cuda", dtype=cd).permute(1, 0, 2)
+        so = (o.stride(0), o.stride(1))
+        lse = torch.empty(N * L, device="cuda")
+        fwd = lambda: ops.attn_fwd(dt, N, 1, L, L, E, q.data_ptr(), st, k.data_ptr(), st,
+                                   v.data_ptr(), st, o.data_ptr(), so, scale, lse)
+        t = {0: [], 1: []}
+        try:
+            for _ in range(rounds):
+                for on in (0, 1):
+                    lib.jmt_attn_set_fwd_rows(on)
+                    t[on].append(timeit(fwd, reps))
+        finally:
+            lib.jmt_attn_set_fwd_rows(-1)
+        u = 4.0 * N * L * L * E
+        r = {"N": N, "L": L, "rounds": rounds}
+        for on, name in ((0, "rows64"), (1, "rows128")):
+            med = statistics.median(t[on])
+            r[name + "_us"] = {"median": round(med, 1), "min": round(min(t[on]), 1),
+                               "max": round(max(t[on]), 1)}
+            r[name + "_frac"] = round(u / med / 1e6 / PEAK, 4)
+        r["below_range"] = r["rows128_us"]["median"] < r["rows64_us"]["min"]
+        print(json.dumps(r), flush=True)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 2:
+    if len(sys.argv) > 1 and sys.argv[1] == "fwd-ab":
+        fwd_ab(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
+    elif len(sys.argv) > 2:
         run(int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 20,
             len(sys.argv) > 4 and sys.argv[4] == "alias")
     else:

@@ -57,7 +57,7 @@ def family(name: str):
         return "attn_short_fwd"
     if "attn_short_bwd" in name:
         return "attn_short_bwd"
-    if "attn_fwd_kernel" in name:
+    if "attn_fwd_kernel" in name or "attn_fwd_rows_kernel" in name:
         return "attn_fwd"
     if "attn_bwd_kernel" in name or "attn_bwd_pds_kernel" in name:
         return "attn_bwd"
