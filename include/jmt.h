@@ -389,6 +389,42 @@ int jmt_sgd_step_amp_zero(int64_t n, float* param, float* grad, float* momentum_
 int jmt_amp_update(float* amp, float growth_factor, float backoff_factor, int growth_interval,
                    void* stream);
 
+/* Device-resident optimizer state (additive to ABI 7): the step kernels below read the learning
+ * rate and Adam's bias corrections from an fp32[8] device block instead of kernel arguments, so
+ * a captured hipGraph follows a schedule (write state[0] between replays) without re-capture.
+ *   state[0]  lr
+ *   state[1]  step: the count of applied steps (fp32: exact to 2^24, then it stays there; both
+ *             bias corrections are 1.0 in fp32 long before)
+ *   state[2]  step_size = lr / (1 - beta1^step)
+ *   state[3]  bc2_sqrt  = sqrt(1 - beta2^step)
+ *   state[4..7] reserved, zero
+ * jmt_opt_tick (one thread; call it before jmt_adam_step): step += 1, then slots 2 and 3 in
+ * double, rounded once to fp32; nothing happens when amp != NULL and amp[2] (found_inf) != 0.
+ * The betas are doubles because torch forms 1 - beta and beta^step in Python doubles: a beta
+ * rounded to fp32 first would put 1 - beta2 off by 5e-5 relative.
+ *
+ * jmt_adam_step: torch.optim.Adam (L2 weight decay added to the gradient; amsgrad iff
+ * max_exp_avg_sq != NULL) over flat fp32 buffers:
+ *   g = grad * gs (+ wd p);  m += (1 - b1)(g - m);  v = b2 v + (1 - b2) g g;  vmax = max(vmax, v)
+ *   p -= step_size * m / (sqrt(v or vmax) / bc2_sqrt + eps)
+ * gs = grad_scale, or amp[1] when amp != NULL; then a found_inf step updates nothing (with
+ * zero_grad the gradient is still zeroed).  zero_grad != 0: grad[i] = 0 in the same pass.
+ * shadow (NULL or bf16/f16 per shadow_dt) receives the new parameters.  param, grad and the
+ * moment buffers must be 16-B aligned, shadow 8-B aligned (JMT_ERR_ARG otherwise).
+ *
+ * jmt_sgd_step_dev: jmt_sgd_step{,_zero,_amp,_amp_zero} with lr = state[0]; amp nullable (then
+ * first-step rule first_step && steps_taken == 0), zero_grad a flag; same alignment rules.  The
+ * result is bit-identical to those entry points at the same fp32 lr. */
+int jmt_opt_tick(float* state, double beta1, double beta2, const float* amp, void* stream);
+int jmt_adam_step(int64_t n, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
+                  float* max_exp_avg_sq, const float* state, double beta1, double beta2,
+                  float eps, float weight_decay, float grad_scale, const float* amp,
+                  int zero_grad, void* shadow, int shadow_dt, void* stream);
+int jmt_sgd_step_dev(int64_t n, float* param, float* grad, float* momentum_buf,
+                     const float* state, float momentum, float dampening, float weight_decay,
+                     int nesterov, int first_step, float grad_scale, const float* amp,
+                     int zero_grad, void* shadow, int shadow_dt, void* stream);
+
 /* ------------------------------------------------------------------ validation post-processing
  * val.py:313-382 + EvaluationMetrics/cccmetric.py:4-21 on the GPU.
  * Per-video float64 arrays live in one flat buffer; video v occupies [off[v], off[v]+seglen[v]).

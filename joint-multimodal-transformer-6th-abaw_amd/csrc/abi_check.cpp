@@ -144,6 +144,53 @@ int main() {
   expect_err("sgd_amp_zero null", jmt_sgd_step_amp_zero(10, fnull, fnull, fnull, 0.1f, 0.9f,
                                                         0.f, 0.f, 1, 1, nullptr, nullptr,
                                                         JMT_BF16, nullptr));
+  // device-resident optimizer state: tick, Adam, SGD with lr = state[0]
+  float* fal = (float*)algn;
+  expect_err("opt_tick null state", jmt_opt_tick(nullptr, 0.9, 0.999, nullptr, nullptr));
+  expect_msg("opt_tick null state", "null state");
+  expect_err("opt_tick beta", jmt_opt_tick(fal, 1.0, 0.999, nullptr, nullptr));
+  expect_err("adam null param", jmt_adam_step(10, fnull, fal, fal, fal, nullptr, fal, 0.9, 0.999,
+                                              1e-8f, 0.f, 1.f, nullptr, 0, nullptr, JMT_BF16,
+                                              nullptr));
+  expect_msg("adam null param", "null pointer");
+  expect_err("adam null moments", jmt_adam_step(10, fal, fal, fnull, fnull, nullptr, fal, 0.9,
+                                                0.999, 1e-8f, 0.f, 1.f, nullptr, 0, nullptr,
+                                                JMT_BF16, nullptr));
+  expect_err("adam null state", jmt_adam_step(10, fal, fal, fal, fal, nullptr, nullptr, 0.9,
+                                              0.999, 1e-8f, 0.f, 1.f, nullptr, 0, nullptr,
+                                              JMT_BF16, nullptr));
+  expect_msg("adam null state", "null state");
+  expect_err("adam amsgrad null state", jmt_adam_step(10, fal, fal, fal, fal, fal, nullptr, 0.9,
+                                                      0.999, 1e-8f, 0.f, 1.f, nullptr, 1, nullptr,
+                                                      JMT_BF16, nullptr));
+  expect_msg("adam amsgrad null state", "null state");
+  expect_err("adam misaligned param", jmt_adam_step(10, (float*)(buf + 4), fal, fal, fal, nullptr,
+                                                    fal, 0.9, 0.999, 1e-8f, 0.f, 1.f, nullptr, 0,
+                                                    nullptr, JMT_BF16, nullptr));
+  expect_msg("adam misaligned param", "16-B aligned");
+  expect_err("adam shadow_dt", jmt_adam_step(10, fal, fal, fal, fal, nullptr, fal, 0.9, 0.999,
+                                             1e-8f, 0.f, 1.f, nullptr, 0, algn, JMT_F32, nullptr));
+  expect_msg("adam shadow_dt", "shadow_dt");
+  expect_err("adam misaligned shadow", jmt_adam_step(10, fal, fal, fal, fal, nullptr, fal, 0.9,
+                                                     0.999, 1e-8f, 0.f, 1.f, nullptr, 0,
+                                                     (void*)(buf + 2), JMT_BF16, nullptr));
+  expect_msg("adam misaligned shadow", "8-B aligned");
+  expect_err("sgd_dev null", jmt_sgd_step_dev(10, fnull, fal, fal, fal, 0.9f, 0.f, 0.f, 1, 1, 1.f,
+                                              nullptr, 0, nullptr, JMT_BF16, nullptr));
+  expect_err("sgd_dev null state", jmt_sgd_step_dev(10, fal, fal, fal, nullptr, 0.9f, 0.f, 0.f, 1,
+                                                    1, 1.f, nullptr, 1, nullptr, JMT_BF16,
+                                                    nullptr));
+  expect_msg("sgd_dev null state", "null state");
+  expect_err("sgd_dev momentum buffer", jmt_sgd_step_dev(10, fal, fal, fnull, fal, 0.9f, 0.f, 0.f,
+                                                         1, 1, 1.f, nullptr, 0, nullptr, JMT_BF16,
+                                                         nullptr));
+  expect_err("sgd_dev misaligned param", jmt_sgd_step_dev(10, (float*)(buf + 4), fal, fal, fal,
+                                                          0.9f, 0.f, 0.f, 1, 1, 1.f, nullptr, 0,
+                                                          nullptr, JMT_BF16, nullptr));
+  expect_msg("sgd_dev misaligned param", "16-B aligned");
+  expect_err("sgd_dev shadow_dt", jmt_sgd_step_dev(10, fal, fal, fal, fal, 0.9f, 0.f, 0.f, 1, 1,
+                                                   1.f, nullptr, 0, algn, 9, nullptr));
+  expect_msg("sgd_dev shadow_dt", "shadow_dt");
   expect_err("vp_ccc null", jmt_vp_ccc(10, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
   expect_err("gather null", jmt_gather_rows(JMT_F32, JMT_BF16, 4, 512, nullptr, 512, 4, nullptr,
                                             nullptr, 512, nullptr));

@@ -148,6 +148,12 @@ _PROTOS = {
                              c_vp, c_int, c_vp]),
     "jmt_sgd_step_zero": (c_int, [c_i64, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_f, c_int, c_int, c_f,
                                   c_vp, c_int, c_vp]),
+    # device-resident optimizer state (csrc/adam.hip): fp32[8] = lr, step, step_size, bc2_sqrt
+    "jmt_opt_tick": (c_int, [c_vp, C.c_double, C.c_double, c_vp, c_vp]),
+    "jmt_adam_step": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_double, C.c_double,
+                              c_f, c_f, c_f, c_vp, c_int, c_vp, c_int, c_vp]),
+    "jmt_sgd_step_dev": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_int, c_int, c_f,
+                                 c_vp, c_int, c_vp, c_int, c_vp]),
 }
 
 EXPORTED = tuple(_PROTOS)

@@ -10,7 +10,9 @@ convention) read into the fusion model, optimizer and window shape this framewor
 * fusion_model(cfg): Two_transformers built as main.py:473-481 (vision_in_ft = 512: the R2D1 /
   ResNet18 features, main.py:469);
 * sgd_kwargs(cfg): the `opt__*` SGD hyper-parameters (instantiator.py:30-36, the reference's
-  optimizer for name_optimizer == "sgd");
+  optimizer for name_optimizer == "sgd"); adam_kwargs(cfg): the Adam ones (instantiator.py:40-46);
+* optimizer(cfg, params): (FusedSGD with a device lr | FusedAdam, lr scheduler or None) as
+  instantiator.get_optimizer_for_params pairs them; scheduler(cfg, opt) is its second half;
 * window(cfg): (batch_size, T) of a training batch: T = seq_length // subseq_length clips.
 """
 from __future__ import annotations
@@ -109,6 +111,71 @@ def sgd_kwargs(cfg: dict) -> Dict[str, float]:
                 dampening=float(mp["opt__dampening"]),
                 weight_decay=float(mp["opt__weight_decay"]),
                 nesterov=str2bool(mp["opt__nesterov"]))
+
+
+def adam_kwargs(cfg: dict) -> dict:
+    """The `opt__*` Adam hyper-parameters (instantiator.py:40-46)."""
+    mp = cfg["model_params"]
+    return dict(lr=float(mp["opt__lr"]), betas=(float(mp["opt__beta1"]), float(mp["opt__beta2"])),
+                eps=float(mp["opt__eps_adam"]), weight_decay=float(mp["opt__weight_decay"]),
+                amsgrad=str2bool(mp["opt__amsgrad"]))
+
+
+def _need(mp: dict, key: str, what: str):
+    if key not in mp:
+        raise KeyError(f"{key} (model_params) is required by {what}")
+    return mp[key]
+
+
+def scheduler(cfg: dict, opt):
+    """The lr scheduler of instantiator.py:52-107 on `opt` (anything with get_lr / set_lr), or
+    None when `opt__lr_scheduler` is off.  `mycosine` needs `opt__coef` (not in the shipped
+    file) and `max_epochs`, `multistep` needs `opt__milestones`: KeyError naming the key."""
+    from . import lr_scheduler as S
+    mp = cfg["model_params"]
+    if not str2bool(mp.get("opt__lr_scheduler", False)):
+        return None
+    name = str(mp["opt__name_lr_scheduler"]).lower()
+    last = int(mp.get("opt__last_epoch", -1))
+    what = f"opt__name_lr_scheduler {name!r}"
+    if name == "step":
+        return S.StepLR(opt, step_size=int(_need(mp, "opt__step_size", what)),
+                        gamma=float(_need(mp, "opt__gamma", what)), last_epoch=last)
+    if name == "cosine":
+        return S.CosineAnnealingLR(opt, T_max=int(_need(mp, "opt__t_max", what)),
+                                   eta_min=float(_need(mp, "opt__min_lr", what)), last_epoch=last)
+    if name == "mystep":
+        return S.MyStepLR(opt, step_size=int(_need(mp, "opt__step_size", what)),
+                          gamma=float(_need(mp, "opt__gamma", what)), last_epoch=last,
+                          min_lr=float(_need(mp, "opt__min_lr", what)))
+    if name == "mycosine":
+        return S.MyCosineLR(opt, coef=float(_need(mp, "opt__coef", what)),
+                            max_epochs=int(_need(mp, "max_epochs", what)),
+                            min_lr=float(_need(mp, "opt__min_lr", what)), last_epoch=last)
+    if name == "multistep":
+        return S.MultiStepLR(opt, milestones=_need(mp, "opt__milestones", what),
+                             gamma=float(_need(mp, "opt__gamma", what)), last_epoch=last)
+    if name == "reduce_on_plateau":
+        raise NotImplementedError("opt__name_lr_scheduler 'reduce_on_plateau': a schedule driven "
+                                  "by the validation metric is not implemented")
+    raise ValueError(f"opt__name_lr_scheduler {name!r} is not one of step, cosine, mystep, "
+                     "mycosine, multistep")
+
+
+def optimizer(cfg: dict, params, **kw):
+    """(optimizer, scheduler or None) as instantiator.get_optimizer_for_params builds them:
+    FusedSGD with the lr on the device (so the schedule reaches a captured step) or FusedAdam by
+    `opt__name_optimizer`, the scheduler by `opt__lr_scheduler` / `opt__name_lr_scheduler`.  kw
+    goes to the optimizer (shadow_dtype, fuse_zero_grad)."""
+    from . import optim
+    name = str(cfg["model_params"].get("opt__name_optimizer", "sgd")).lower()
+    if name == "sgd":
+        opt = optim.FusedSGD(params, device_lr=True, **sgd_kwargs(cfg), **kw)
+    elif name == "adam":
+        opt = optim.FusedAdam(params, **adam_kwargs(cfg), **kw)
+    else:
+        raise ValueError(f"opt__name_optimizer {name!r} is neither 'sgd' nor 'adam'")
+    return opt, scheduler(cfg, opt)
 
 
 def window(cfg: dict, split: str = "train_params") -> Tuple[int, int]:

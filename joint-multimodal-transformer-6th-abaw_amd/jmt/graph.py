@@ -8,7 +8,9 @@ Requirements the JMT path meets by construction:
   * static inputs: the caller keeps the input / label tensors alive and refills them in place;
   * no host synchronisation inside the step (the losses stay on device);
   * optimizer state lives in persistent buffers (jmt.optim.FusedSGD's flat buffers) and its
-    first-step branch has been taken before capture (the warm-up steps run eagerly);
+    first-step branch has been taken before capture (the warm-up steps run eagerly); capture
+    bakes kernel arguments in, so an lr that is to change between replays must live in the
+    optimizer's device state block (FusedSGD(device_lr=True), FusedAdam; jmt.lr_scheduler);
   * every launch goes to torch's current stream (jmt.ops) — under capture that is the capture
     stream; the concurrent branch streams (jmt.streams) fork from and join back into it.
 """

@@ -1,15 +1,17 @@
-"""Fused SGD over flat buffers (instantiator.py:32-38 semantics, config_file.json:73-80).
+"""Fused SGD and Adam over flat buffers (instantiator.py:32-46 semantics, config_file.json:73-82).
 
 All trainable parameters are re-homed into ONE flat fp32 buffer, their gradients into another
-(the buffer the RCCL all-reduce runs on), the momentum into a third; one jmt_sgd_step launch
-updates everything and rewrites the bf16/f16 compute shadows of the weights in the same pass.
+(the buffer the RCCL all-reduce runs on), the momentum (Adam: both moments) into further ones;
+one jmt_sgd_step / jmt_adam_step launch updates everything and rewrites the bf16/f16 compute
+shadows of the weights in the same pass.  With the device state block (FusedSGD(device_lr=True),
+FusedAdam) the learning rate is read on the device, so a captured step follows a schedule.
 Parameters that never receive a gradient (the reference's unused `final_encoder`,
 `gated_attention`) must not be passed: torch.optim.SGD skips them because their .grad is None,
 so `used_parameters()` finds them with one probe backward."""
 from __future__ import annotations
 
 import os
-from typing import Iterable, List, Optional
+from typing import Iterable, List, Optional, Tuple
 
 import torch
 
@@ -22,22 +24,36 @@ def _bump_grad_gen(_p):
     F._grad_gen[0] += 1
 
 
-class FusedSGD:
-    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, momentum: float = 0.0,
-                 dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
-                 shadow_dtype: Optional[torch.dtype] = None, fuse_zero_grad: bool = False):
-        """fuse_zero_grad: the step kernel zeroes each gradient after reading it (jmt_sgd_step_zero)
-        and the next zero_grad() issues nothing while no gradient has been written since — the
-        training step of train.py:96-315 without a fill launch.  Off by default: torch's
-        optimizer.step() leaves .grad readable until zero_grad().
+def _state_block(lr: float, dev) -> torch.Tensor:
+    """The device optimizer state of include/jmt.h: fp32[8] = lr, step, step_size, bc2_sqrt, 4
+    reserved."""
+    return torch.tensor([lr, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
 
-        Contract of the skipped fill: "written since" is known from functional._grad_gen, which
-        the HIP gradient writers (functional._grad_buffer) and torch autograd's accumulation into
-        .grad (post-accumulate hooks) bump.  Anything else that writes into a .grad in place
-        (p.grad.add_/copy_ by hand, a helper writing into the flat views) is invisible to it and
-        the next backward would add onto the stale values: call zero_grad(force=True) after such
-        a write, or set JMT_CHECK_ZERO_GRAD=1 to have every skipped fill verify (one reduction +
-        host sync) that the gradients are in fact zero."""
+
+class _FlatOptimizer:
+    """The flat-buffer layout the fused optimizers share: every parameter re-homed into one fp32
+    buffer (each starting on a 64-element boundary, the padding zero), its .grad into a second,
+    the 16-bit compute shadows into a third; the gradient-write bookkeeping behind
+    fuse_zero_grad; the optional device state block (`state`) with set_lr / get_lr.
+
+    fuse_zero_grad: the step kernel zeroes each gradient after reading it and the next
+    zero_grad() issues nothing while no gradient has been written since — the training step of
+    train.py:96-315 without a fill launch.  Off by default: torch's optimizer.step() leaves .grad
+    readable until zero_grad().
+
+    Contract of the skipped fill: "written since" is known from functional._grad_gen, which the
+    HIP gradient writers (functional._grad_buffer) and torch autograd's accumulation into .grad
+    (post-accumulate hooks) bump.  Anything else that writes into a .grad in place
+    (p.grad.add_/copy_ by hand, a helper writing into the flat views) is invisible to it and the
+    next backward would add onto the stale values: call zero_grad(force=True) after such a
+    write, or set JMT_CHECK_ZERO_GRAD=1 to have every skipped fill verify (one reduction + host
+    sync) that the gradients are in fact zero."""
+
+    state: Optional[torch.Tensor] = None
+    _BUFFERS: tuple = ()          # names of the per-element state buffers (state_dict)
+
+    def _init_flat(self, params: Iterable[torch.nn.Parameter], lr: float,
+                   shadow_dtype: Optional[torch.dtype], fuse_zero_grad: bool):
         self.params: List[torch.nn.Parameter] = list(params)
         assert self.params, "no parameters"
         dev = self.params[0].device
@@ -48,11 +64,9 @@ class FusedSGD:
             offs.append(n)
             n += -(-p.numel() // 64) * 64
         self.numel = n
-        self.lr, self.momentum, self.dampening = lr, momentum, dampening
-        self.weight_decay, self.nesterov = weight_decay, nesterov
+        self.lr = lr
         self.flat_p = torch.empty(n, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.buf = torch.zeros(n, dtype=torch.float32, device=dev) if momentum else None
         self.shadow = (torch.empty(n, dtype=shadow_dtype, device=dev)
                        if shadow_dtype not in (None, torch.float32) else None)
         self.flat_p.zero_()
@@ -71,7 +85,6 @@ class FusedSGD:
         for p, off in zip(self.params, offs):
             F.register_shadow(p, self.shadow[off:off + p.numel()].view_as(p)
                               if self.shadow is not None else None)
-        self.first = True
         self.fuse_zero_grad = bool(fuse_zero_grad)
         # the gradients are known to be zero while nothing has written one since the last fill /
         # zeroing step (functional._grad_gen counts the HIP writers; torch autograd accumulation
@@ -106,9 +119,105 @@ class FusedSGD:
         elif os.environ.get("JMT_CHECK_ZERO_GRAD", "0") == "1":
             nz = int(torch.count_nonzero(self.flat_g))
             if nz:
-                raise RuntimeError(f"FusedSGD.zero_grad: {nz} gradient element(s) written outside "
-                                   "the tracked writers since the fused zeroing step (see the "
-                                   "fuse_zero_grad contract); call zero_grad(force=True)")
+                raise RuntimeError(f"{type(self).__name__}.zero_grad: {nz} gradient element(s) "
+                                   "written outside the tracked writers since the fused zeroing "
+                                   "step (see the fuse_zero_grad contract); call "
+                                   "zero_grad(force=True)")
+
+    def set_lr(self, lr: float):
+        """Set the learning rate.  With the device state block this is a stream-ordered fill of
+        state[0]: no host synchronisation, legal between replays of a captured step, and the
+        replays that follow use the new value.  Without it (FusedSGD(device_lr=False)) only the
+        host value changes: the lr is a kernel argument, so a graph captured earlier does NOT
+        see it and keeps stepping at the lr it was captured with."""
+        self.lr = float(lr)
+        if self.state is not None:
+            self.state[0:1].fill_(self.lr)
+
+    def get_lr(self) -> float:
+        """The learning rate last set (the host's copy: nothing is read from the device)."""
+        return self.lr
+
+    def _ptr(self, t: Optional[torch.Tensor]):
+        return t.data_ptr() if t is not None else None
+
+    def _shadow_dt(self) -> int:
+        return ops.dt(self.shadow) if self.shadow is not None else _lib.BF16
+
+    # ---------------------------------------------------------------- resume
+    def _host_state(self) -> dict:
+        return {}
+
+    def _load_host_state(self, sd: dict):
+        pass
+
+    def state_dict(self) -> dict:
+        """A flat dict: copies of the parameter buffer, the per-element state buffers and the
+        device state block, plus the host-side scalars."""
+        sd = {"kind": type(self).__name__, "numel": self.numel, "lr": self.lr,
+              "flat_p": self.flat_p.clone(),
+              "state": self.state.clone() if self.state is not None else None}
+        for name in self._BUFFERS:
+            t = getattr(self, name)
+            sd[name] = t.clone() if t is not None else None
+        sd.update(self._host_state())
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict):
+        """Copy a state_dict() into this optimizer's own buffers (their addresses, and so a
+        captured graph, stay valid) and rewrite the compute shadows."""
+        if sd.get("kind") != type(self).__name__ or sd.get("numel") != self.numel:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: state of "
+                             f"{sd.get('kind')} with {sd.get('numel')} elements does not fit "
+                             f"{self.numel}")
+        for name in self._BUFFERS + ("state",):
+            mine, theirs = getattr(self, name), sd.get(name)
+            if (mine is None) != (theirs is None):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: buffer {name!r} is "
+                                 "present on one side only")
+            if mine is not None:
+                mine.copy_(theirs)
+        self.flat_p.copy_(sd["flat_p"])
+        if self.shadow is not None:
+            ops.cast(self.flat_p, self.shadow.dtype, out=self.shadow)
+        self.lr = float(sd["lr"])
+        self._load_host_state(sd)
+
+
+class FusedSGD(_FlatOptimizer):
+    _BUFFERS = ("buf",)
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, momentum: float = 0.0,
+                 dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                 shadow_dtype: Optional[torch.dtype] = None, fuse_zero_grad: bool = False,
+                 device_lr: bool = False):
+        """fuse_zero_grad: see _FlatOptimizer (jmt_sgd_step_zero).
+
+        device_lr: the learning rate lives in the device state block and the step goes through
+        jmt_sgd_step_dev, so set_lr() (an lr scheduler) takes effect inside a captured graph.
+        Off by default: the lr is then a kernel argument, fixed at capture."""
+        self._init_flat(params, lr, shadow_dtype, fuse_zero_grad)
+        self.momentum, self.dampening = momentum, dampening
+        self.weight_decay, self.nesterov = weight_decay, nesterov
+        dev = self.flat_p.device
+        self.buf = torch.zeros(self.numel, dtype=torch.float32, device=dev) if momentum else None
+        self.state = _state_block(lr, dev) if device_lr else None
+        self.first = True
+
+    def _host_state(self) -> dict:
+        return {"first": self.first, "amp": getattr(self, "_amp", False)}
+
+    def _load_host_state(self, sd: dict):
+        self.first = bool(sd["first"])
+        self._amp = bool(sd["amp"])
+
+    def _step_dev(self, grad_scale: float, amp_state: Optional[torch.Tensor]):
+        _lib.call("jmt_sgd_step_dev", self.numel, self.flat_p.data_ptr(), self.flat_g.data_ptr(),
+                  self._ptr(self.buf), self.state.data_ptr(), self.momentum, self.dampening,
+                  self.weight_decay, int(self.nesterov), int(self.first), grad_scale,
+                  self._ptr(amp_state), int(self.fuse_zero_grad), self._ptr(self.shadow),
+                  self._shadow_dt(), ops.stream())
 
     @torch.no_grad()
     def step_amp(self, amp_state: torch.Tensor):
@@ -116,6 +225,10 @@ class FusedSGD:
         the momentum buffer is initialised is then decided on the device (steps_taken), so plain
         step() calls cannot follow scaled ones."""
         self._amp = True
+        if self.state is not None:
+            self._step_dev(1.0, amp_state)
+            self._clean_gen = F._grad_gen[0]
+            return
         fn = "jmt_sgd_step_amp_zero" if self.fuse_zero_grad else "jmt_sgd_step_amp"
         _lib.call(fn, self.numel, self.flat_p.data_ptr(), self.flat_g.data_ptr(),
                   self.buf.data_ptr() if self.buf is not None else None, self.lr, self.momentum,
@@ -130,17 +243,66 @@ class FusedSGD:
         if getattr(self, "_amp", False):
             raise RuntimeError("FusedSGD: step() after GradScaler steps (first-step state is on "
                                "the device); keep using scaler.step(opt)")
-        ops.sgd_step(self.flat_p, self.flat_g, self.buf, self.lr, self.momentum, self.dampening,
-                     self.weight_decay, self.nesterov, self.first, grad_scale, self.shadow,
-                     zero_grad=self.fuse_zero_grad)
+        if self.state is not None:
+            self._step_dev(grad_scale, None)
+        else:
+            ops.sgd_step(self.flat_p, self.flat_g, self.buf, self.lr, self.momentum,
+                         self.dampening, self.weight_decay, self.nesterov, self.first, grad_scale,
+                         self.shadow, zero_grad=self.fuse_zero_grad)
         self.first = False
         self._clean_gen = F._grad_gen[0]
 
 
+class FusedAdam(_FlatOptimizer):
+    """torch.optim.Adam (L2 weight decay; amsgrad optional) over the flat buffers, as
+    instantiator.py:40-46 configures it.  The lr, the step count and both bias corrections live
+    in the device state block: a step is two launches (jmt_opt_tick, jmt_adam_step), reads
+    nothing from the device on the host, and captures into a hipGraph that follows set_lr()."""
+
+    _BUFFERS = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, amsgrad: bool = False,
+                 shadow_dtype: Optional[torch.dtype] = None, fuse_zero_grad: bool = False):
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"FusedAdam: betas {betas} must be in [0, 1)")
+        self._init_flat(params, lr, shadow_dtype, fuse_zero_grad)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), eps
+        self.weight_decay, self.amsgrad = weight_decay, bool(amsgrad)
+        dev = self.flat_p.device
+        self.exp_avg = torch.zeros(self.numel, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(self.numel, dtype=torch.float32, device=dev)
+        self.max_exp_avg_sq = (torch.zeros(self.numel, dtype=torch.float32, device=dev)
+                               if self.amsgrad else None)
+        self.state = _state_block(lr, dev)
+
+    def _step(self, grad_scale: float, amp_state: Optional[torch.Tensor]):
+        st, amp, s = self.state.data_ptr(), self._ptr(amp_state), ops.stream()
+        _lib.call("jmt_opt_tick", st, self.betas[0], self.betas[1], amp, s)
+        _lib.call("jmt_adam_step", self.numel, self.flat_p.data_ptr(), self.flat_g.data_ptr(),
+                  self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                  self._ptr(self.max_exp_avg_sq), st, self.betas[0], self.betas[1], self.eps,
+                  self.weight_decay, grad_scale, amp, int(self.fuse_zero_grad),
+                  self._ptr(self.shadow), self._shadow_dt(), s)
+        self._clean_gen = F._grad_gen[0]
+
+    @torch.no_grad()
+    def step_amp(self, amp_state: torch.Tensor):
+        """One step driven by a GradScaler's device state: unscale by amp[1]; on found_inf
+        neither the step count nor any buffer changes."""
+        self._step(1.0, amp_state)
+
+    @torch.no_grad()
+    def step(self, grad_scale: float = 1.0):
+        self._step(grad_scale, None)
+
+
 class GradScaler:
-    """torch.cuda.amp.GradScaler semantics (train.py:89,314-316) for FusedSGD with the whole
-    state on the device: `scaler.scale(loss).backward(); scaler.step(opt); scaler.update()` issue
-    kernels only (no host synchronisation; the step stays capturable into a hipGraph)."""
+    """torch.cuda.amp.GradScaler semantics (train.py:89,314-316) for FusedSGD / FusedAdam with the
+    whole state on the device: `scaler.scale(loss).backward(); scaler.step(opt);
+    scaler.update()` issue kernels only (no host synchronisation; the step stays capturable into
+    a hipGraph)."""
 
     def __init__(self, init_scale: float = 2.0 ** 16, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, growth_interval: int = 2000, device=None):
@@ -153,7 +315,7 @@ class GradScaler:
     def scale(self, loss: torch.Tensor) -> torch.Tensor:
         return loss * self.state[0]
 
-    def step(self, opt: "FusedSGD"):
+    def step(self, opt: "_FlatOptimizer"):
         _lib.call("jmt_amp_check", opt.numel, opt.flat_g.data_ptr(), self.state.data_ptr(),
                   ops.stream())
         opt.step_amp(self.state)
