@@ -110,6 +110,25 @@ void jmt_gemm_set_debug(int flags);
  * the last launch made with debug flag 8; returns the number of blocks copied to host[4*n]. */
 int jmt_gemm_trace_read(uint64_t* host, int nblocks);
 
+/* Grouped weight gradients: up to 16 problems of different shapes, leading dimensions and
+ * pointer tables as the (tile, split) items of ONE persistent split-K launch and one reduce
+ * launch.  Each problem is a jmt_gemm_desc of the form the training step's weight gradients
+ * take: 16-bit A and B (one dtype and one majorness per group), fp32 C with any alpha / beta,
+ * M and N multiples of 256, K a multiple of 64 (>= 256), batch1 = 1, operand modes 0, 1 and 3,
+ * optional dbias_tab (NULL entries allowed; MN-major A and B, K >= 512).  bias, relu, aux, fp32
+ * operands, other sizes or a 16-bit C return JMT_ERR_UNSUPPORTED before anything is launched
+ * (the caller runs jmt_gemm on that problem).  desc.workspace / dbias_ws are ignored: the group
+ * shares `workspace` (jmt_gemm_grouped_workspace_bytes, 16-B aligned).
+ * desc.splits: 0 lets the group's planner choose — one target item length for the whole group,
+ * so that the items of all problems fill the persistent grid in whole rounds; >= 1 forces that
+ * problem's split count.  A problem with one split writes C in the GEMM's epilogue and takes no
+ * slab.  jmt_gemm_grouped_plan reports the split counts (splits_out[n]); a problem's C and row
+ * sums have the bits of jmt_gemm on it alone, on the split-K ping-pong kernel, at that count. */
+int jmt_gemm_grouped(const jmt_gemm_desc* descs, int n, void* workspace, size_t ws_bytes,
+                     void* stream);
+size_t jmt_gemm_grouped_workspace_bytes(const jmt_gemm_desc* descs, int n);
+int jmt_gemm_grouped_plan(const jmt_gemm_desc* descs, int n, int* splits_out);
+
 /* ------------------------------------------------------------------ row-wise ops
  * Rows are `rows` vectors of length D at stride ld (elements). */
 

@@ -79,6 +79,55 @@ int main() {
     fprintf(stderr, "FAIL planners ws=%zu splits=%d\n", ws, splits);
     ++g_fail;
   }
+  // grouped weight gradients: everything outside the grouped form is refused before any launch
+  {
+    jmt_gemm_desc gd[2];
+    memset(gd, 0, sizeof(gd));
+    for (int i = 0; i < 2; ++i) {
+      gd[i].ab_dtype = JMT_BF16; gd[i].c_dtype = JMT_F32; gd[i].M = 512; gd[i].N = 256;
+      gd[i].K = 1024 * (i + 1); gd[i].n_a = gd[i].n_b = gd[i].n_c = 1;
+      gd[i].batch0 = gd[i].batch1 = 1; gd[i].lda = 512; gd[i].ldb = 256; gd[i].ldc = 256;
+      gd[i].alpha = 1.f; gd[i].beta = 1.f; gd[i].a[0] = gd[i].b[0] = gd[i].c[0] = algn;
+    }
+    int sp[2] = {0, 0};
+    if (jmt_gemm_grouped_plan(gd, 2, sp) != JMT_OK || sp[0] < 1 || sp[1] < 1 ||
+        jmt_gemm_grouped_workspace_bytes(gd, 2) == 0) {
+      fprintf(stderr, "FAIL grouped plan: %s\n", jmt_last_error());
+      ++g_fail;
+    }
+    expect_err("grouped null descs", jmt_gemm_grouped(nullptr, 2, nullptr, 0, nullptr));
+    expect_err("grouped 17 problems", jmt_gemm_grouped(gd, 17, nullptr, 0, nullptr));
+    expect_err("grouped no workspace", jmt_gemm_grouped(gd, 2, nullptr, 0, nullptr));
+    expect_msg("grouped no workspace", "workspace bytes");
+#define GRP_UNSUP(what, set, reset)                                              \
+    do {                                                                         \
+      set;                                                                       \
+      const int rc_ = jmt_gemm_grouped(gd, 2, algn, (size_t)1 << 40, nullptr);   \
+      expect_err(what, rc_);                                                     \
+      if (rc_ != JMT_ERR_UNSUPPORTED) {                                          \
+        fprintf(stderr, "FAIL %s: rc=%d, not JMT_ERR_UNSUPPORTED\n", what, rc_); \
+        ++g_fail;                                                                \
+      }                                                                          \
+      reset;                                                                     \
+    } while (0)
+    GRP_UNSUP("grouped fp32 operands", gd[1].ab_dtype = JMT_F32, gd[1].ab_dtype = JMT_BF16);
+    GRP_UNSUP("grouped M % 256", gd[1].M = 384, gd[1].M = 512);
+    GRP_UNSUP("grouped N % 256", gd[0].N = 128, gd[0].N = 256);
+    GRP_UNSUP("grouped K % 64", gd[0].K = 1000, gd[0].K = 1024);
+    GRP_UNSUP("grouped bias", gd[1].bias = (const float*)algn, gd[1].bias = nullptr);
+    GRP_UNSUP("grouped relu", gd[0].relu = 1, gd[0].relu = 0);
+    GRP_UNSUP("grouped aux", gd[1].aux = algn, gd[1].aux = nullptr);
+    GRP_UNSUP("grouped 16-bit C", gd[1].c_dtype = JMT_BF16, gd[1].c_dtype = JMT_F32);
+    GRP_UNSUP("grouped mixed majorness", gd[1].a_kmajor = 1, gd[1].a_kmajor = 0);
+    GRP_UNSUP("grouped K-concat mode 2", gd[0].a_mode = 2, gd[0].a_mode = 0);
+    GRP_UNSUP("grouped batch1", gd[0].batch1 = 2, gd[0].batch1 = 1);
+#undef GRP_UNSUP
+    gd[0].c[0] = misal;
+    expect_err("grouped misaligned C", jmt_gemm_grouped(gd, 2, algn, (size_t)1 << 40, nullptr));
+    gd[0].c[0] = algn; gd[0].n_dbias = 1; gd[0].dbias_tab[0] = nullptr;
+    expect_err("grouped dbias null entry", jmt_gemm_grouped(gd, 2, algn, (size_t)1 << 40, nullptr));
+    expect_msg("grouped dbias null entry", "every dbias_tab entry");
+  }
 
   // row ops
   expect_err("l2norm_fwd null", jmt_l2norm_fwd(JMT_BF16, JMT_BF16, 8, 512, nullptr, 512, nullptr,

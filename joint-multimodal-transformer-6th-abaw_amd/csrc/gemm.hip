@@ -888,3 +888,262 @@ extern "C" int jmt_gemm(const jmt_gemm_desc* d, void* stream) {
   }
   return JMT_OK;
 }
+
+// ------------------------------------------------------------------ grouped weight gradients
+// jmt_gemm_grouped (gemm_persist.hip: gemm_group_kernel, group_reduce_kernel).  Planning is a
+// pure host function: ONE target item length L (K-tiles) for the whole group, splits_p =
+// round(K-tiles_p / L) (at least 1 — 2 with row sums, whose partials the reduce folds — and at
+// least 4 K-tiles per split), L chosen by the cost of the launch it gives:
+//   rounds x (kKtUs x longest item + kItemUs) + kSlabUs x (items that write a slab)
+// with rounds = ceil(items / grid): the persistent grid runs whole rounds, so an L whose item
+// count just misses a multiple of the grid pays a whole round for the remainder.  kKtUs: one
+// 256 x 256 x 64 K-tile at the 840-860 TFLOP/s the ping-pong split kernel reaches on its
+// well-filled weight gradients; kItemUs: pipeline prologue + slab epilogue of an item; kSlabUs:
+// the reduce's read of one 256 KiB slab (15.7 us per 252-slab launch).
+namespace {
+
+constexpr double kKtUs = 2.5, kItemUs = 8.0, kSlabUs = 0.065;
+
+struct GroupPlan {
+  int splits[GRP_MAXPROB];
+  int64_t ws_off[GRP_MAXPROB], rs_off[GRP_MAXPROB];   // floats
+  int64_t ws_floats;
+  int items;
+  bool rs;
+};
+
+// jmt_gemm's normalisation of a split count (whole K-tiles per split), to its fixed point
+int norm_splits(int K, int s) {
+  for (int it = 0; it < 8; ++it) {
+    int kps = ((K + s - 1) / s + 63) / 64 * 64;
+    if (kps < 64) kps = 64;
+    const int s2 = (K + kps - 1) / kps;
+    if (s2 == s) break;
+    s = s2;
+  }
+  return s < 1 ? 1 : s;
+}
+
+int group_check_one(const jmt_gemm_desc* d, const jmt_gemm_desc* d0, int i, int& pool) {
+#define JMT_GRP_UNSUP(cond, ...) \
+  do { if (!(cond)) return set_error(JMT_ERR_UNSUPPORTED, __VA_ARGS__); } while (0)
+  const int dt = d->ab_dtype;
+  JMT_CHECK_ARG(dt == JMT_F32 || dt == JMT_BF16 || dt == JMT_F16,
+                "jmt_gemm_grouped: problem %d: bad ab_dtype %d", i, dt);
+  JMT_GRP_UNSUP(dt != JMT_F32, "jmt_gemm_grouped: problem %d: fp32 operands", i);
+  JMT_GRP_UNSUP(d->c_dtype == JMT_F32, "jmt_gemm_grouped: problem %d: c_dtype must be fp32", i);
+  JMT_GRP_UNSUP(dt == d0->ab_dtype && !d->a_kmajor == !d0->a_kmajor &&
+                    !d->b_kmajor == !d0->b_kmajor,
+                "jmt_gemm_grouped: problem %d: one operand dtype and layout per group", i);
+  JMT_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "jmt_gemm_grouped: problem %d: empty size", i);
+  JMT_GRP_UNSUP(d->M % 256 == 0 && d->N % 256 == 0 && d->K % 64 == 0 && d->K >= 256,
+                "jmt_gemm_grouped: problem %d: M and N must be multiples of 256, K of 64 (>= 256)",
+                i);
+  JMT_GRP_UNSUP(d->bias == nullptr && d->n_bias == 0 && !d->relu && d->aux == nullptr,
+                "jmt_gemm_grouped: problem %d: bias, relu and aux are not supported", i);
+  JMT_GRP_UNSUP(d->batch1 <= 1, "jmt_gemm_grouped: problem %d: batch1 must be 1", i);
+  const int batch0 = d->batch0 < 1 ? 1 : d->batch0;
+  JMT_CHECK_ARG(d->n_a >= 1 && d->n_a <= MAXP && d->n_b >= 1 && d->n_b <= MAXP && d->n_c >= 1 &&
+                    d->n_c <= MAXP && d->n_dbias >= 0 && d->n_dbias <= MAXP,
+                "jmt_gemm_grouped: problem %d: pointer table size", i);
+  JMT_GRP_UNSUP((d->a_mode == 0 || d->a_mode == 1 || d->a_mode == 3) &&
+                    (d->b_mode == 0 || d->b_mode == 1 || d->b_mode == 3) &&
+                    (d->c_mode == 0 || d->c_mode == 1),
+                "jmt_gemm_grouped: problem %d: operand modes 0, 1 and 3 only", i);
+  JMT_CHECK_ARG(d->lda > 0 && d->ldb > 0 && d->ldc > 0 && d->lda < (1LL << 31) &&
+                    d->ldb < (1LL << 31) && d->ldc < (1LL << 31) && d->lda % 8 == 0 &&
+                    d->ldb % 8 == 0 && d->ldc % 4 == 0 && d->sA0 % 8 == 0 && d->sB0 % 8 == 0 &&
+                    d->sC0 % 4 == 0,
+                "jmt_gemm_grouped: problem %d: leading dimensions / strides (multiples of 8 "
+                "elements for A and B, 4 for C, below 2^31)", i);
+  for (int k = 0; k < d->n_a; ++k)
+    JMT_CHECK_ARG(d->a[k] && ((uintptr_t)d->a[k] & 15) == 0,
+                  "jmt_gemm_grouped: problem %d: A[%d] null or not 16-B aligned", i, k);
+  for (int k = 0; k < d->n_b; ++k)
+    JMT_CHECK_ARG(d->b[k] && ((uintptr_t)d->b[k] & 15) == 0,
+                  "jmt_gemm_grouped: problem %d: B[%d] null or not 16-B aligned", i, k);
+  for (int k = 0; k < d->n_c; ++k)
+    JMT_CHECK_ARG(d->c[k] && ((uintptr_t)d->c[k] & 15) == 0,
+                  "jmt_gemm_grouped: problem %d: C[%d] null or not 16-B aligned", i, k);
+  const int need_a = d->a_mode == 3 ? 0 : (d->a_mode == 1 ? batch0 : 1);
+  const int need_b = d->b_mode == 3 ? 0 : (d->b_mode == 1 ? batch0 : 1);
+  JMT_CHECK_ARG(d->n_a >= need_a && d->n_b >= need_b && d->n_c >= (d->c_mode == 1 ? batch0 : 1),
+                "jmt_gemm_grouped: problem %d: pointer table < batch0", i);
+  if (d->a_mode == 3)
+    JMT_CHECK_ARG(d->a_kseg > 0 && d->a_kseg % 64 == 0 &&
+                      d->n_a >= batch0 * ((d->K + d->a_kseg - 1) / d->a_kseg),
+                  "jmt_gemm_grouped: problem %d: A per-batch K-concat needs kseg a multiple of 64 "
+                  "and batch0 x ceil(K / kseg) pointers", i);
+  if (d->b_mode == 3)
+    JMT_CHECK_ARG(d->b_kseg > 0 && d->b_kseg % 64 == 0 &&
+                      d->n_b >= batch0 * ((d->K + d->b_kseg - 1) / d->b_kseg),
+                  "jmt_gemm_grouped: problem %d: B per-batch K-concat needs kseg a multiple of 64 "
+                  "and batch0 x ceil(K / kseg) pointers", i);
+  if (d->n_dbias > 0) {
+    JMT_CHECK_ARG(!d->a_kmajor && !d->b_kmajor && d->n_dbias >= batch0,
+                  "jmt_gemm_grouped: problem %d: A row sums need MN-major A and B and a dbias "
+                  "table of batch0 entries", i);
+    bool any = false;
+    for (int k = 0; k < batch0; ++k) any = any || d->dbias_tab[k] != nullptr;
+    JMT_CHECK_ARG(any, "jmt_gemm_grouped: problem %d: every dbias_tab entry is null", i);
+    JMT_GRP_UNSUP(d->K >= 512 && d->splits != 1,
+                  "jmt_gemm_grouped: problem %d: row sums need at least 2 splits (K >= 512)", i);
+  }
+  if (d->splits > 1)
+    JMT_GRP_UNSUP((d->K / 64) / norm_splits(d->K, d->splits) >= 2,
+                  "jmt_gemm_grouped: problem %d: fewer than 2 K-tiles per split", i);
+  pool += d->n_a + d->n_b + d->n_c + d->n_dbias;
+  JMT_GRP_UNSUP(pool <= GRP_POOL, "jmt_gemm_grouped: more than %d table pointers in the group",
+                GRP_POOL);
+#undef JMT_GRP_UNSUP
+  return JMT_OK;
+}
+
+int group_plan(const jmt_gemm_desc* descs, int n, GroupPlan& pl) {
+  JMT_CHECK_ARG(descs != nullptr, "jmt_gemm_grouped: null descriptors");
+  JMT_CHECK_ARG(n >= 1 && n <= GRP_MAXPROB, "jmt_gemm_grouped: 1 to %d problems", GRP_MAXPROB);
+  int pool = 0;
+  for (int i = 0; i < n; ++i) {
+    const int rc = group_check_one(descs + i, descs, i, pool);
+    if (rc != JMT_OK) return rc;
+  }
+  const int G = num_cus_persist();
+  long tiles[GRP_MAXPROB];
+  int nkt[GRP_MAXPROB], smin[GRP_MAXPROB], maxkt = 4;
+  pl.rs = false;
+  for (int i = 0; i < n; ++i) {
+    const jmt_gemm_desc& d = descs[i];
+    tiles[i] = (long)(d.M / 256) * (d.N / 256) * (d.batch0 < 1 ? 1 : d.batch0);
+    nkt[i] = d.K / 64;
+    smin[i] = d.n_dbias > 0 ? 2 : 1;
+    pl.rs = pl.rs || d.n_dbias > 0;
+    if (nkt[i] > maxkt) maxkt = nkt[i];
+  }
+  auto splits_at = [&](int i, int L) {
+    if (descs[i].splits >= 1) return norm_splits(descs[i].K, descs[i].splits);   // forced
+    int s = (nkt[i] + L / 2) / L;
+    if (s > nkt[i] / 4) s = nkt[i] / 4;
+    if (s < smin[i]) s = smin[i];
+    return norm_splits(descs[i].K, s);
+  };
+  double best = 1e300;
+  int bestL = maxkt;
+  for (int L = maxkt; L >= 4; --L) {          // ties keep the longer items (fewer slabs)
+    long items = 0, slabs = 0;
+    int longest = 0;
+    for (int i = 0; i < n; ++i) {
+      const int s = splits_at(i, L);
+      items += tiles[i] * s;
+      if (s > 1) slabs += tiles[i] * s;
+      const int len = (nkt[i] + s - 1) / s;
+      if (len > longest) longest = len;
+    }
+    const long rounds = (items + G - 1) / G;
+    const double c = rounds * (kKtUs * longest + kItemUs) + kSlabUs * slabs;
+    if (c < best * 0.999) { best = c; bestL = L; }
+  }
+  int64_t off = 0;
+  long items = 0;
+  for (int i = 0; i < n; ++i) {
+    const jmt_gemm_desc& d = descs[i];
+    const int s = splits_at(i, bestL);
+    pl.splits[i] = s;
+    pl.ws_off[i] = off;
+    if (s > 1) off += (int64_t)s * (d.batch0 < 1 ? 1 : d.batch0) * d.M * (int64_t)d.N;
+    items += tiles[i] * s;
+  }
+  for (int i = 0; i < n; ++i) {
+    const jmt_gemm_desc& d = descs[i];
+    pl.rs_off[i] = off;
+    if (pl.rs) off += (int64_t)pl.splits[i] * (d.batch0 < 1 ? 1 : d.batch0) * d.M;
+  }
+  JMT_CHECK_ARG(items < (1L << 30), "jmt_gemm_grouped: too many items");
+  pl.items = (int)items;
+  pl.ws_floats = off;
+  return JMT_OK;
+}
+
+}  // namespace
+
+extern "C" int jmt_gemm_grouped_plan(const jmt_gemm_desc* descs, int n, int* splits_out) {
+  GroupPlan pl;
+  const int rc = group_plan(descs, n, pl);
+  if (rc != JMT_OK) return rc;
+  if (splits_out)
+    for (int i = 0; i < n; ++i) splits_out[i] = pl.splits[i];
+  return JMT_OK;
+}
+
+extern "C" size_t jmt_gemm_grouped_workspace_bytes(const jmt_gemm_desc* descs, int n) {
+  GroupPlan pl;
+  if (group_plan(descs, n, pl) != JMT_OK) return 0;
+  return (size_t)pl.ws_floats * sizeof(float);
+}
+
+extern "C" int jmt_gemm_grouped(const jmt_gemm_desc* descs, int n, void* workspace,
+                                size_t ws_bytes, void* stream) {
+  GroupPlan pl;
+  const int rc = group_plan(descs, n, pl);
+  if (rc != JMT_OK) return rc;
+  JMT_CHECK_ARG(pl.ws_floats == 0 ||
+                    (workspace != nullptr && ((uintptr_t)workspace & 15) == 0 &&
+                     ws_bytes >= (size_t)pl.ws_floats * sizeof(float)),
+                "jmt_gemm_grouped: needs %zu 16-B aligned workspace bytes",
+                (size_t)pl.ws_floats * sizeof(float));
+  GroupParams g = {};
+  g.ws = (float*)workspace;
+  g.nprob = n;
+  g.dbg = g_gemm_dbg;
+  int pool = 0, item = 0, rblk = 0;
+  for (int i = 0; i < n; ++i) {
+    const jmt_gemm_desc& d = descs[i];
+    GroupProb& P = g.prob[i];
+    const int batch0 = d.batch0 < 1 ? 1 : d.batch0;
+    P.sA0 = d.a_mode == 3 ? (d.K + d.a_kseg - 1) / d.a_kseg : d.sA0;   // mode 3: segments per b0
+    P.sB0 = d.b_mode == 3 ? (d.K + d.b_kseg - 1) / d.b_kseg : d.sB0;
+    P.sC0 = d.sC0;
+    P.ws_off = pl.ws_off[i];
+    P.rs_off = pl.rs_off[i];
+    P.lda = (int)d.lda; P.ldb = (int)d.ldb; P.ldc = (int)d.ldc;
+    P.M = d.M; P.N = d.N; P.K = d.K;
+    P.batch0 = batch0;
+    P.splits = pl.splits[i];
+    P.tiles_m = d.M / 256;
+    P.tiles_n = d.N / 256;
+    P.a_mode = d.a_mode; P.b_mode = d.b_mode; P.c_mode = d.c_mode;
+    P.a_kseg = d.a_mode == 3 ? d.a_kseg : 0;
+    P.b_kseg = d.b_mode == 3 ? d.b_kseg : 0;
+    P.a_off = pool;
+    for (int k = 0; k < d.n_a; ++k) g.pool[pool++] = d.a[k];
+    P.b_off = pool;
+    for (int k = 0; k < d.n_b; ++k) g.pool[pool++] = d.b[k];
+    P.c_off = pool;
+    for (int k = 0; k < d.n_c; ++k) g.pool[pool++] = d.c[k];
+    P.d_off = d.n_dbias > 0 ? pool : -1;
+    for (int k = 0; k < d.n_dbias; ++k) g.pool[pool++] = d.dbias_tab[k];
+    P.item0 = item;
+    item += P.tiles_m * P.tiles_n * batch0 * P.splits;
+    P.rblk0 = rblk;
+    if (P.splits > 1) {
+      const int64_t groups = (int64_t)d.M * d.N * batch0 / 4;
+      int64_t nb = (groups + 255) / 256;
+      if (nb > 2048) nb = 2048;
+      P.rblk_n = (int)nb;
+    }
+    rblk += P.rblk_n;
+    P.dbias_acc = d.dbias_acc;
+    P.alpha = d.alpha;
+    P.beta = d.beta;
+  }
+  g.W = item;
+  hipStream_t st = as_stream(stream);
+  const int ncu = num_cus_persist();
+  launch_gemm_group(g, descs[0].ab_dtype, descs[0].a_kmajor, descs[0].b_kmajor, pl.rs,
+                    item < ncu ? item : ncu, st);
+  JMT_LAUNCH_CHECK("jmt_gemm_grouped");
+  if (rblk > 0) {
+    launch_group_reduce(g, rblk, st);
+    JMT_LAUNCH_CHECK("jmt_gemm_grouped(reduce)");
+  }
+  return JMT_OK;
+}

@@ -1077,6 +1077,361 @@ __global__ __launch_bounds__(512) void gemm_pp_split_kernel(GemmParams p) {
   else pp2_run<T, AK, BK, 0, 1, SPL>(p, lbase, smem, nullptr, nm, W);
 }
 
+// ------------------------------------------------------------------ grouped split-K ping-pong
+// jmt_gemm_grouped: the split-K ping-pong schedule above (pp2_run: phases, DMA stream, deadline
+// counts unchanged) over the items of SEVERAL weight-gradient problems.  What changes is where an
+// item's operands come from: logical item L of the launch belongs to the problem p with
+// prob[p].item0 <= L < prob[p + 1].item0; within a problem the order is pwalk's (tile fastest,
+// then split, then batch entry), so the tiles of one (batch, split) are consecutive and land on
+// one XCD.  The problem's record (GroupProb, in the kernel arguments) is read with scalar loads
+// when a cursor moves to its next item.
+//
+// The vmcnt counting rule at the head of this file holds across a problem switch because the
+// epilogue's VMEM count per item does not depend on the problem: every item issues TM * TN 16-B
+// stores (+ 2 row-sum stores when any problem of the launch takes row sums: problems without
+// dbias store theirs into their own partial area, which nobody reads), whether they go to a slab
+// or, for a problem with splits == 1, straight to C.  The beta * C loads of that direct form are
+// extra operations the deadline counts do not include: an undercount only waits for more.
+struct GItem {
+  int pi, m0, n0, b0, sp, kt0, len;
+};
+
+__device__ __forceinline__ GItem gitem(const GroupParams& g, int w) {
+  const int W = g.W;
+  const int x = w & 7, q = W >> 3, r = W & 7;
+  const int L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (w >> 3);
+  int pi = 0;
+  for (int i = 1; i < g.nprob; ++i) pi = L >= g.prob[i].item0 ? i : pi;
+  pi = __builtin_amdgcn_readfirstlane(pi);
+  const GroupProb& P = g.prob[pi];
+  const int l = L - P.item0;
+  const int ntile = P.tiles_m * P.tiles_n;
+  const int bs = l / ntile, t = l - bs * ntile;
+  const int mt = t / P.tiles_n;
+  GItem it;
+  it.pi = pi;
+  it.m0 = mt * 256;
+  it.n0 = (t - mt * P.tiles_n) * 256;
+  it.b0 = bs / P.splits;
+  it.sp = bs - it.b0 * P.splits;
+  const int nkt = P.K >> 6;                   // split sp: K-tiles [sp nkt / S, (sp + 1) nkt / S)
+  it.kt0 = it.sp * nkt / P.splits;
+  it.len = (it.sp + 1) * nkt / P.splits - it.kt0;
+  return it;
+}
+
+// SPL: 1 fp32 slabs (direct C where splits == 1), 2 + the A row sums
+template <typename T, bool AK, bool BK, int GRP, int SPL>
+__device__ __forceinline__ void ppg_run(const GroupParams& g, uint32_t lbase, const char* smem,
+                                        int nm) {
+  using C = CfgPP;
+  typedef typename Frag16<T>::t F;
+  constexpr bool ISA = GRP == 1;                           // this group's operand: A (else B)
+  constexpr bool KM = ISA ? AK : BK;
+  constexpr int EPO = C::TM * C::TN + (SPL == 2 ? 2 : 0);  // VMEM operations of one epilogue
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wl = wid & 3;
+  constexpr int wm = GRP;
+  const int wn = wl;
+  const int G = gridDim.x;
+  int nT = 0;                                              // K-tiles of this block's items
+  for (int k = 0; k < nm; ++k) nT += gitem(g, blockIdx.x + k * G).len;
+  const int nh = 2 * nT;
+  int rowv[2][2], kkv[2][2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+      chunk_src<T, KM, 64, 256>((8 * h + 2 * wl + e) * 64 + lane, rowv[h][e], kkv[h][e]);
+
+  // the issue stream; dk / hk / left follow its current problem
+  GItem iss_it = gitem(g, blockIdx.x);
+  int iss_k = 0, iss_kt = 0, left = 0;
+  int64_t dk = 0, hk = 0;
+  const char* ps[2][2];
+  auto set_stream = [&]() {
+    const GroupProb& P = g.prob[iss_it.pi];
+    const int64_t ld = ISA ? P.lda : P.ldb;
+    const int mode = ISA ? P.a_mode : P.b_mode;
+    const int kseg = ISA ? P.a_kseg : P.b_kseg;
+    dk = (KM ? (int64_t)64 : (int64_t)64 * ld) * (int64_t)sizeof(T);
+    hk = dk / 2;
+    const int k0 = (iss_it.kt0 + iss_kt) * 64;
+    int kl;
+    const T* X = operand_base<T>(g.pool + (ISA ? P.a_off : P.b_off), mode, ISA ? P.sA0 : P.sB0,
+                                 0, iss_it.b0, 0, kseg, k0, kl);
+    const int r0 = ISA ? iss_it.m0 : iss_it.n0;
+    const char* sx = (const char*)(KM ? X + (int64_t)r0 * ld + kl : X + (int64_t)kl * ld + r0);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+        ps[h][e] = sx + (KM ? (int64_t)rowv[h][e] * ld + kkv[h][e]
+                            : (int64_t)kkv[h][e] * ld + rowv[h][e]) * (int64_t)sizeof(T);
+    left = (mode >= 2 ? kseg / 64 : 1 << 30) - (kl >> 6);
+  };
+  auto next_ktile = [&]() {
+    if (++iss_kt == iss_it.len) {
+      iss_kt = 0;
+      if (++iss_k < nm) {
+        iss_it = gitem(g, blockIdx.x + iss_k * G);
+        set_stream();
+      }
+    } else if (--left == 0) {
+      set_stream();
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) ps[h][e] += dk;
+    }
+  };
+  auto issue = [&](int kh_) {
+    const uint32_t dst = lbase + (kh_ & 3) * PP_SLOT + (ISA ? 0 : 16384) + 2 * wl * 1024;
+    const int64_t kh = (kh_ & 1) ? hk : 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) glds16_at(ps[h][e] + kh, dst + (8 * h + e) * 1024);
+  };
+  bool ep_cur = false, ep_prev = false;
+  // dbg 32: the epilogue's stores are not counted, so every wait drains them too (the guard of
+  // the counts: results must not change)
+  const int epo = (g.dbg & 32) ? 0 : EPO;
+  auto deadline = [&](int kh_) {                           // as pp2_run
+    if (kh_ >= nh) return;
+    const int m = kh_ - 1;
+    if constexpr (GRP == 0) {
+      const int n = (m + 2 < nh ? 4 : 0) + (ep_cur ? epo : 0);
+      if (n == 4) wait_vmcnt<4>();
+      else wait_vm_le(n);
+    } else {
+      const int n = (m + 2 < nh ? 4 : 0) + (m + 3 < nh ? 4 : 0) +
+                    ((ep_prev ? 1 : 0) + (ep_cur ? 1 : 0)) * epo;
+      if (n == 8) wait_vmcnt<8>();
+      else wait_vm_le(n);
+    }
+  };
+
+  set_stream();
+  if constexpr (GRP == 0) {
+    issue(0);
+    issue(1);
+    wait_vmcnt<4>();
+  } else {
+    issue(0);
+    if (nh > 1) issue(1);
+    if (nh > 2) {
+      next_ktile();
+      issue(2);
+    }
+    wait_vm_le((nh > 1 ? 4 : 0) + (nh > 2 ? 4 : 0));
+  }
+  __builtin_amdgcn_s_barrier();
+  if constexpr (GRP == 1) __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+
+  f32x4 acc[C::TM][C::TN];
+#pragma unroll
+  for (int i = 0; i < C::TM; ++i)
+#pragma unroll
+    for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  F fa[8] = {}, fb[4] = {};
+  GItem cur = gitem(g, blockIdx.x);
+  int cur_k = 0, cur_left = cur.len;
+  float rsum[2] = {0.f, 0.f};
+  auto epilogue = [&]() {
+    const GroupProb& P = g.prob[cur.pi];
+    const int gq = lane >> 4, rl = lane & 15;
+    const bool direct = P.splits == 1;
+    float* base;
+    int64_t stride;
+    if (direct) {
+      base = P.c_mode == 1 ? (float*)const_cast<void*>(g.pool[P.c_off + cur.b0])
+                           : (float*)const_cast<void*>(g.pool[P.c_off]) + (int64_t)cur.b0 * P.sC0;
+      stride = P.ldc;
+    } else {
+      base = g.ws + P.ws_off + ((int64_t)cur.sp * P.batch0 + cur.b0) * (int64_t)P.M * P.N;
+      stride = P.N;
+    }
+    float* const sl = base + (int64_t)(cur.m0 + wm * C::WTM + rl) * stride + cur.n0 +
+                      wn * C::WTN + 4 * gq;
+    const float al = direct ? P.alpha : 1.f;               // slabs hold the raw partial sums
+    if (direct && P.beta != 0.f) {
+      const float be = P.beta;
+#pragma unroll
+      for (int i = 0; i < C::TM; ++i) {
+        float* const row = sl + (int64_t)(16 * i) * stride;
+        f32x4 c[C::TN];
+#pragma unroll
+        for (int j = 0; j < C::TN; ++j) c[j] = *(const f32x4*)(row + 16 * j);
+#pragma unroll
+        for (int j = 0; j < C::TN; ++j) {
+          f32x4 x = acc[i][j] * al;
+          x += be * c[j];
+          __builtin_nontemporal_store(x, (f32x4*)(row + 16 * j));
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < C::TM; ++i) {
+        float* const row = sl + (int64_t)(16 * i) * stride;
+#pragma unroll
+        for (int j = 0; j < C::TN; ++j)
+          __builtin_nontemporal_store(acc[i][j] * al, (f32x4*)(row + 16 * j));
+      }
+    }
+    if constexpr (SPL == 2) {
+      float* const rs = g.ws + P.rs_off + ((int64_t)cur.sp * P.batch0 + cur.b0) * P.M + cur.m0 +
+                        wm * C::WTM + 16 * wn + rl;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        float v = rsum[h];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        if (lane < 16) rs[64 * h] = v;
+        rsum[h] = 0.f;
+      }
+    }
+  };
+  for (int t = 0; t < nT; ++t) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int m = 2 * t + ks;
+      ep_prev = ep_cur;
+      ep_cur = false;
+      if (ks == 0) {
+        if (cur_left == 0) {                               // previous item done: its epilogue
+          epilogue();
+          ep_cur = true;
+#pragma unroll
+          for (int i = 0; i < C::TM; ++i)
+#pragma unroll
+            for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          cur = gitem(g, blockIdx.x + (++cur_k) * G);
+          cur_left = cur.len;
+        }
+        --cur_left;
+      }
+      if ((GRP == 0 && ks == 0) || (GRP == 1 && ks == 1)) next_ktile();
+      const char* slot = smem + (m & 3) * PP_SLOT;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        fb[j] = read_frag16<T, BK, 64, 256>(slot + 16384, wn * C::WTN + 16 * j, 0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        fa[i] = read_frag16<T, AK, 64, 256>(slot, wm * C::WTM + 16 * i, 0);
+      {
+        const int kh_ = m + (GRP == 0 ? 2 : 3);
+        if (kh_ < nh) issue(kh_);
+      }
+      if constexpr (GRP == 1) deadline(m + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(fb[j], fa[i], acc[i][j]);
+      __builtin_amdgcn_s_setprio(0);
+      if constexpr (SPL == 2) {                            // A row sums, sub-tiles wn and wn + 4
+        if (wn == 0) { rsum[0] = rowsum8(fa[0], rsum[0]); rsum[1] = rowsum8(fa[4], rsum[1]); }
+        else if (wn == 1) { rsum[0] = rowsum8(fa[1], rsum[0]); rsum[1] = rowsum8(fa[5], rsum[1]); }
+        else if (wn == 2) { rsum[0] = rowsum8(fa[2], rsum[0]); rsum[1] = rowsum8(fa[6], rsum[1]); }
+        else { rsum[0] = rowsum8(fa[3], rsum[0]); rsum[1] = rowsum8(fa[7], rsum[1]); }
+      }
+      if constexpr (GRP == 0) deadline(m + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  if constexpr (GRP == 0) __builtin_amdgcn_s_barrier();
+  epilogue();
+}
+
+template <typename T, bool AK, bool BK, int SPL>
+__global__ __launch_bounds__(512) void gemm_group_kernel(GroupParams g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int G = gridDim.x;
+  const int nm = (g.W - (int)blockIdx.x + G - 1) / G;
+  if (nm <= 0) return;
+  const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  if ((threadIdx.x >> 6) < 4) ppg_run<T, AK, BK, 0, SPL>(g, lbase, smem, nm);
+  else ppg_run<T, AK, BK, 1, SPL>(g, lbase, smem, nm);
+}
+
+// The group's reduce: block blockIdx.x serves the problem whose [rblk0, rblk0 + rblk_n) holds
+// it; per 4 consecutive outputs the splits' slabs are summed in split order, then alpha and
+// beta * C, and the thread of column 0 folds the row-sum partials — the operations and order of
+// reduce_outputs<float, 4>, so a problem's result has the bits of jmt_gemm on it alone at the
+// same split count.  Problems with splits == 1 wrote C in the GEMM and have no blocks here.
+__global__ __launch_bounds__(256) void group_reduce_kernel(GroupParams g) {
+  int pi = 0;
+  for (int i = 1; i < g.nprob; ++i) pi = (int)blockIdx.x >= g.prob[i].rblk0 ? i : pi;
+  const GroupProb& P = g.prob[pi];
+  const int nb = P.batch0, S = P.splits;
+  const int64_t per = (int64_t)P.M * P.N;
+  const int64_t total = per * nb / 4;
+  const int64_t sstride = (int64_t)nb * per;
+  const float* const ws = g.ws + P.ws_off;
+  for (int64_t e = (int64_t)((int)blockIdx.x - P.rblk0) * 256 + threadIdx.x; e < total;
+       e += (int64_t)P.rblk_n * 256) {
+    const int64_t idx = e * 4;
+    const int b = (int)(idx / per);
+    const int64_t mn = idx - (int64_t)b * per;
+    const int m = (int)(mn / P.N), n = (int)(mn - (int64_t)m * P.N);
+    const float* src0 = ws + (int64_t)b * per + mn;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    int s = 0;
+    for (; s + 8 <= S; s += 8) {
+      float4 t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t[u] = *(const float4*)(src0 + (s + u) * sstride);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        v[0] += t[u].x; v[1] += t[u].y; v[2] += t[u].z; v[3] += t[u].w;
+      }
+    }
+    for (; s < S; ++s) {
+      const float4 t = *(const float4*)(src0 + s * sstride);
+      v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
+    }
+    if (P.d_off >= 0 && n == 0 && g.pool[P.d_off + b]) {   // the A row sums' split partials
+      const float* src = g.ws + P.rs_off + (int64_t)b * P.M + m;
+      const int64_t ts = (int64_t)nb * P.M;
+      float r = 0.f;
+      int t = 0;
+      for (; t + 8 <= S; t += 8) {
+        float x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = src[(t + u) * ts];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) r += x[u];
+      }
+      for (; t < S; ++t) r += src[t * ts];
+      float* d = (float*)const_cast<void*>(g.pool[P.d_off + b]);
+      d[m] = (P.dbias_acc ? d[m] : 0.f) + r;
+    }
+    float* cp = P.c_mode == 1 ? (float*)const_cast<void*>(g.pool[P.c_off + b])
+                              : (float*)const_cast<void*>(g.pool[P.c_off]) + (int64_t)b * P.sC0;
+    float* const co = cp + (int64_t)m * P.ldc + n;
+    float4 cin = {0.f, 0.f, 0.f, 0.f};
+    if (P.beta != 0.f) cin = *(const float4*)co;
+    const float ci[4] = {cin.x, cin.y, cin.z, cin.w};
+    float out[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float x = v[i] * P.alpha;
+      if (P.beta != 0.f) x += P.beta * ci[i];
+      out[i] = x;
+    }
+    *(float4*)co = float4{out[0], out[1], out[2], out[3]};
+  }
+}
+
 // the persistent configuration (gemm_persist_kernel): cfg 40 = Cfg5's tile (128-B K-tiles, 2
 // stages).  (Cfg20's 64-B K-tiles in 4 stages with interleaved DMA issue — "cfg 41" — and a
 // three-deep A ring with the bias from scalar loads — "cfg 42" — measured slower on every step
@@ -1210,6 +1565,33 @@ void launch_gemm_pp_split(const GemmParams& p, int dt, int ak, int bk, bool rs, 
                           hipStream_t st) {
   if (dt == JMT_BF16) launch_pp_split_l<__bf16>(p, ak, bk, rs, blocks, st);
   else launch_pp_split_l<_Float16>(p, ak, bk, rs, blocks, st);
+}
+
+template <typename T, bool AK, bool BK>
+static void launch_group_t(const GroupParams& g, bool rs, int blocks, hipStream_t st) {
+  void (*fn)(GroupParams) = rs ? gemm_group_kernel<T, AK, BK, 2> : gemm_group_kernel<T, AK, BK, 1>;
+  (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024);
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(512), (size_t)PP_NSLOT * PP_SLOT, st, g);
+}
+
+template <typename T>
+static void launch_group_l(const GroupParams& g, int ak, int bk, bool rs, int blocks,
+                           hipStream_t st) {
+  if (ak && bk) launch_group_t<T, true, true>(g, rs, blocks, st);
+  else if (ak) launch_group_t<T, true, false>(g, rs, blocks, st);
+  else if (bk) launch_group_t<T, false, true>(g, rs, blocks, st);
+  else launch_group_t<T, false, false>(g, rs, blocks, st);
+}
+
+void launch_gemm_group(const GroupParams& g, int dt, int ak, int bk, bool rs, int blocks,
+                       hipStream_t st) {
+  if (dt == JMT_BF16) launch_group_l<__bf16>(g, ak, bk, rs, blocks, st);
+  else launch_group_l<_Float16>(g, ak, bk, rs, blocks, st);
+}
+
+void launch_group_reduce(const GroupParams& g, int blocks, hipStream_t st) {
+  hipLaunchKernelGGL(group_reduce_kernel, dim3(blocks), dim3(256), 0, st, g);
 }
 
 // cfg 44 eligibility (also the planner's split choice, pp_split_plan): 16-bit A / B, whole

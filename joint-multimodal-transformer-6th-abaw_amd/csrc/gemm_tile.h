@@ -702,4 +702,37 @@ void launch_gemm_pp_split(const GemmParams& p, int dt, int ak, int bk, bool rs, 
 bool pp_split_ok(int dt, int M, int N, int K, int splits);
 int pp_split_plan(int dt, int M, int N, int K, int batch);
 
+// ------------------------------------------------------------------ grouped weight gradients
+// jmt_gemm_grouped: several weight-gradient problems (16-bit A / B, fp32 C, whole 256 x 256
+// tiles, batch1 = 1) as the items of ONE split-K ping-pong launch and one reduce launch.  The
+// kernel arguments hold one record per problem and a shared pool for the pointer tables (A / B
+// segments, C and dbias entries) — all read with scalar loads at an item boundary.
+constexpr int GRP_MAXPROB = 16;
+constexpr int GRP_POOL = 216;
+struct GroupProb {
+  int64_t sA0, sB0, sC0;        // batch strides (mode 3: segments per batch entry, as GemmParams)
+  int64_t ws_off, rs_off;       // floats from GroupParams::ws: fp32 slabs [split][b0][M][N]
+                                // (splits > 1) and A row-sum partials [split][b0][M]
+  int lda, ldb, ldc;
+  int M, N, K;
+  int batch0, splits, tiles_m, tiles_n;
+  int a_mode, b_mode, c_mode, a_kseg, b_kseg;
+  int a_off, b_off, c_off, d_off;   // first pool entry of each table; d_off < 0: no row sums
+  int item0;                    // first logical item of the launch (prefix of tiles x b0 x splits)
+  int rblk0, rblk_n;            // the problem's blocks of the reduce launch
+  int dbias_acc;
+  float alpha, beta;
+};
+struct GroupParams {
+  GroupProb prob[GRP_MAXPROB];
+  const void* pool[GRP_POOL];
+  float* ws;
+  int nprob, W, dbg, pad_;
+};
+static_assert(sizeof(GroupParams) <= 4096, "kernel arguments are limited to 4 KiB");
+// gemm_persist.hip: the grouped launch (rs: any problem takes A row sums) and its reduce
+void launch_gemm_group(const GroupParams& g, int dt, int ak, int bk, bool rs, int blocks,
+                       hipStream_t st);
+void launch_group_reduce(const GroupParams& g, int blocks, hipStream_t st);
+
 }  // namespace jmt

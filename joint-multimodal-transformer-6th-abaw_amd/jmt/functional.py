@@ -15,6 +15,8 @@ Layout conventions
 """
 from __future__ import annotations
 
+import contextlib
+
 import math
 import os
 from typing import Optional
@@ -266,11 +268,24 @@ def fused_bgrad_ok(cd) -> bool:
     return _fused_bgrad["on"] and cd in (torch.bfloat16, torch.float16)
 
 
-def _wgrad(G: Rows, n, xin, ld_in, kseg, W, r0, cd, b=None) -> bool:
+def wgrad_group_ok() -> bool:
+    """Whether weight-gradient launches may be queued and flushed grouped (ops.wgrad_scope /
+    defer): not under a GradBucketer, whose buckets complete in the profiled launch order."""
+    return _grad_hook is None and ops.wgrad_group_enabled()
+
+
+def wgrad_scope():
+    """ops.wgrad_scope() where grouping is allowed, else a no-op context."""
+    return ops.wgrad_scope() if wgrad_group_ok() else contextlib.nullcontext()
+
+
+def _wgrad(G: Rows, n, xin, ld_in, kseg, W, r0, cd, b=None, defer: bool = False) -> bool:
     """W.grad[r0:r0+n, s*kseg:...] += dY^T X_s   (split-K over the rows); with `b`, also
     b.grad[r0:r0+n] += the column sums of dY inside the same GEMM when the launch form allows it
     (n > 1, 16-bit; K segments share dY, so only segment 0 sums it).  Returns True when b.grad
-    was written."""
+    was written.  defer: the launch may wait for the end of the backward pass to be flushed with
+    the other deferred weight gradients as one grouped launch — only for callers after which
+    nothing writes dY or the inputs again."""
     gW = _grad_buffer(W)
     if gW is None:
         return False
@@ -281,6 +296,12 @@ def _wgrad(G: Rows, n, xin, ld_in, kseg, W, r0, cd, b=None) -> bool:
         gb = _grad_buffer(b)
         if gb is not None:
             dbt = [gb[r0:r0 + n]] + [None] * (nseg - 1)
+
+    def done():
+        _grad_done(W)
+        if dbt is not None:
+            _grad_done(b)
+
     # A = dY^T (MN-major); for n == 1 the single row is the contiguous dY column (K-major)
     a_ld, a_kmaj = (G.ld, False) if n > 1 else (_vec(cd), True)
     ops.gemm(M=n, N=kseg, K=G.rows, ab_dtype=_dc(cd), c_dtype=F32,
@@ -288,10 +309,8 @@ def _wgrad(G: Rows, n, xin, ld_in, kseg, W, r0, cd, b=None) -> bool:
              b=[x.data_ptr() for x in xin], ldb=ld_in, b_kmajor=False,
              b_mode=1 if nseg > 1 else 0,
              c=[_ptr(gW, r0 * Kin)], ldc=Kin, batch0=nseg, sA=(0, 0), sB=(0, 0),
-             sC=(kseg, 0), beta=1.0, dbias_tab=dbt, device=G.t.device)
-    _grad_done(W)
-    if dbt is not None:
-        _grad_done(b)
+             sC=(kseg, 0), beta=1.0, dbias_tab=dbt, device=G.t.device,
+             done=done, keep=(G.t, gW, *xin, *(dbt or ())), defer=defer and wgrad_group_ok())
     return dbt is not None
 
 
@@ -348,7 +367,9 @@ class LinearFn(Function):
                                                                                   in_dtypes[i])
 
         def param_grads():      # side stream (jmt.streams.run_side)
-            if not _wgrad(Gy, n, xin, L0.ld, kseg, W, r0, cd, b):
+            # no input gradient: nothing runs behind this node that could write gy or the
+            # saved inputs, so the launch may join the end-of-backward group
+            if not _wgrad(Gy, n, xin, L0.ld, kseg, W, r0, cd, b, defer=not any(need)):
                 _bgrad(Gy, n, b, r0)
 
         streams.run_side(param_grads, reads=(Gy.t,) + tuple(xin))

@@ -30,7 +30,7 @@ from torch.autograd import Function
 
 from . import ops, streams
 from .functional import (_dc, _grad_buffer, _grad_done, _ptr, attn_backward, attn_forward,
-                         compute_dtype, weight_as)
+                         compute_dtype, weight_as, wgrad_scope)
 
 _enabled = {"on": os.environ.get("JMT_GROUPED", "1") != "0"}
 # the cross-attention backward's three stream-gradient GEMMs on branch streams: measured
@@ -97,22 +97,25 @@ def _gemm_wgrad(dy_ptrs: Sequence[int], ldy: int, sdy: int, x_ptrs: Sequence[int
     dbt = None
     if bs is not None and n > 1 and fused_bgrad_ok(cd):
         dbt = []
-        for b in bs:
-            gb = _grad_buffer(b)
-            dbt.append(gb[r0:r0 + n] if gb is not None else
+        for b in bs:            # a None entry: no bias gradient for that group (NULL table slot)
+            gb = _grad_buffer(b) if b is not None else None
+            dbt.append(None if b is None else gb[r0:r0 + n] if gb is not None else
                        torch.empty(n, dtype=torch.float32, device=dev))
     Kin = Ws[0].shape[1]
     ta, tb = len(dy_ptrs) > 1, len(x_ptrs) > 1
+
+    def done():
+        _grad_done(*Ws)
+        if dbt is not None:
+            _grad_done(*bs)
+
     ops.gemm(M=n, N=Kin, K=rows, ab_dtype=_dc(cd), c_dtype=ops.F32,
              a=list(dy_ptrs), lda=ldy, a_kmajor=False, a_mode=1 if ta else 0,
              sA=(0 if ta else sdy, 0),
              b=list(x_ptrs), ldb=ldx, b_kmajor=False, b_mode=1 if tb else 0,
              sB=(0 if tb else sx, 0),
              c=[_ptr(g, r0 * Kin) for g in grads], ldc=Kin, c_mode=1, batch0=len(Ws),
-             beta=1.0, dbias_tab=dbt, device=dev)
-    _grad_done(*Ws)
-    if dbt is not None:
-        _grad_done(*bs)
+             beta=1.0, dbias_tab=dbt, device=dev, done=done, keep=(*grads, *(dbt or ())))
     return dbt is not None
 
 
@@ -149,14 +152,17 @@ def _gemm_wgrad_kcat(dy_segs, ldy: int, x_segs, ldx: int, rows: int, n: int, Ws,
             dbt.append(gb[r0:r0 + n] if gb is not None else
                        torch.empty(n, dtype=torch.float32, device=dev))
     Kin = Ws[0].shape[1]
+
+    def done():
+        _grad_done(*Ws)
+        if dbt is not None:
+            _grad_done(*bs)
+
     ops.gemm(M=n, N=Kin, K=nseg * rows, ab_dtype=_dc(cd), c_dtype=ops.F32,
              a=[p for d in dy_segs for p in d], lda=ldy, a_kmajor=False, a_mode=3, a_kseg=rows,
              b=[p for x in x_segs for p in x], ldb=ldx, b_kmajor=False, b_mode=3, b_kseg=rows,
              c=[_ptr(g, r0 * Kin) for g in grads], ldc=Kin, c_mode=1, batch0=len(Ws),
-             beta=1.0, dbias_tab=dbt, device=dev)
-    _grad_done(*Ws)
-    if dbt is not None:
-        _grad_done(*bs)
+             beta=1.0, dbias_tab=dbt, device=dev, done=done, keep=(*grads, *(dbt or ())))
     return dbt is not None
 
 
@@ -250,7 +256,9 @@ class StackJointFn(Function):
         dX = _contig(dX, cd)
         G = Rows(dX[2])
         _dgrad(G, E, W, 0, cd, [dX[0], dX[1]], E, 2, E, beta=1.0)
-        if not _wgrad(G, E, [X[0], X[1]], E, E, W, 0, cd, b):
+        # deferred to the end-of-backward group: dX[2] is read by nobody else (the node hands on
+        # dX[0] / dX[1] only) and X is this node's saved forward buffer
+        if not _wgrad(G, E, [X[0], X[1]], E, E, W, 0, cd, b, defer=True):
             _bgrad(G, E, b, 0)
         dv = dX[0] if vdt == cd else _cast_keep_layout(dX[0], vdt)
         dp = dX[1] if pdt == cd else _cast_keep_layout(dX[1], pdt)
@@ -514,12 +522,14 @@ class EncoderGroupFn(Function):
         merged = _merge_wgrads["on"] and hid == E and 2 * G <= 8 and cd != torch.float32
         if merged:
             ws = [p[6] for p in P] + [p[4] for p in P]
-            bsw = ([] if b2_done else [p[7] for p in P]) + [p[5] for p in P]
+            # b2 already summed (by LN2's backward): its entries stay NULL and W1's bias
+            # gradient is still taken inside the launch
+            bsw = ([None] * G if b2_done else [p[7] for p in P]) + [p[5] for p in P]
             fused = _gemm_wgrad([dS[g].data_ptr() for g in range(G)] +
                                 [dF1[g].data_ptr() for g in range(G)], E, 0,
                                 [F1[g].data_ptr() for g in range(G)] +
                                 [H1[g].data_ptr() for g in range(G)], E, 0, R, E, ws, 0, cd, dev,
-                                bs=None if b2_done else bsw)
+                                bs=bsw)
             if not fused:
                 if not b2_done:
                     _bias_grad_grouped(dS.data_ptr(), G, E, R * E, R, E, [p[7] for p in P], 0,
@@ -718,13 +728,17 @@ class CrossAttention6Fn(Function):
                 bs = [M[m][1] for m in ms]
                 seg = lambda off: [[_ptr(dQKV, i * R * 3 * E + off), _ptr(dQKV, j * R * 3 * E + off)]
                                    for i, j in zip(h0, h1)]
-                fq = _gemm_wgrad_kcat(seg(0), 3 * E,
-                                      [[Y[pairs[i][1]].data_ptr(), Y[pairs[j][1]].data_ptr()]
-                                       for i, j in zip(h0, h1)], E, R, E, ws, 0, cd, dev, bs=bs)
-                fkv = _gemm_wgrad_kcat(seg(E), 3 * E,
-                                       [[Y[pairs[i][2]].data_ptr(), Y[pairs[j][2]].data_ptr()]
-                                        for i, j in zip(h0, h1)], E, R, 2 * E, ws, E, cd, dev,
-                                       bs=bs if fq else None)
+                # the query-row and key / value-row launches sit next to each other: one
+                # grouped launch (their rows of W.grad / b.grad are disjoint)
+                with wgrad_scope():
+                    fq = _gemm_wgrad_kcat(seg(0), 3 * E,
+                                          [[Y[pairs[i][1]].data_ptr(), Y[pairs[j][1]].data_ptr()]
+                                           for i, j in zip(h0, h1)], E, R, E, ws, 0, cd, dev,
+                                          bs=bs)
+                    fkv = _gemm_wgrad_kcat(seg(E), 3 * E,
+                                           [[Y[pairs[i][2]].data_ptr(), Y[pairs[j][2]].data_ptr()]
+                                            for i, j in zip(h0, h1)], E, R, 2 * E, ws, E, cd, dev,
+                                           bs=bs if fq else None)
                 if not (fq and fkv):
                     assert not fq, "query-row bias sums fused without the key / value rows"
                     for m, i, j in zip(ms, h0, h1):
@@ -735,12 +749,13 @@ class CrossAttention6Fn(Function):
             for h in halves:
                 ws = [M[pairs[i][0]][0] for i in h]
                 bs = [M[pairs[i][0]][1] for i in h]
-                fq = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E) for i in h], 3 * E, 0,
-                                 [Y[pairs[i][1]].data_ptr() for i in h], E, 0, R, E, ws, 0, cd,
-                                 dev, bs=bs)
-                fkv = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E + E) for i in h], 3 * E, 0,
-                                  [Y[pairs[i][2]].data_ptr() for i in h], E, 0, R, 2 * E, ws, E,
-                                  cd, dev, bs=bs if fq else None)
+                with wgrad_scope():
+                    fq = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E) for i in h], 3 * E, 0,
+                                     [Y[pairs[i][1]].data_ptr() for i in h], E, 0, R, E, ws, 0,
+                                     cd, dev, bs=bs)
+                    fkv = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E + E) for i in h], 3 * E, 0,
+                                      [Y[pairs[i][2]].data_ptr() for i in h], E, 0, R, 2 * E, ws,
+                                      E, cd, dev, bs=bs if fq else None)
                 if not (fq and fkv):
                     assert not fq, "query-row bias sums fused without the key / value rows"
                     rest.append(h)

@@ -62,9 +62,13 @@ def gemm(*, M: int, N: int, K: int, ab_dtype: int, c_dtype: int,
          alpha: float = 1.0, beta: float = 0.0, bias: Optional[torch.Tensor] = None,
          bias_mode: int = 1, relu: bool = False, aux: Optional[torch.Tensor] = None,
          ldaux: int = 0, splits: Optional[int] = None, bias_tab=None, dbias_tab=None,
-         dbias_acc: bool = True, device=None) -> None:
+         dbias_acc: bool = True, device=None, done=None, keep=(), defer: bool = False) -> None:
     """dbias_tab: per-b0 fp32 outputs (None: skip that entry) that receive (dbias_acc: += ) the
-    row sums of A — a weight-gradient GEMM's bias gradient (jmt_gemm_desc ABI 4)."""
+    row sums of A — a weight-gradient GEMM's bias gradient (jmt_gemm_desc ABI 4).
+    done: called once the launch is enqueued (a weight gradient's completion report).  A launch
+    with `done` may be held in the weight-gradient queue (wgrad_scope, or with defer=True until
+    the end of the running backward pass) and flushed with its neighbours as one
+    jmt_gemm_grouped launch; `keep` are the tensors its operands live in."""
     d = GemmDesc()
     d.ab_dtype, d.c_dtype = ab_dtype, c_dtype
     d.aux_dtype = dt(aux) if aux is not None else c_dtype
@@ -93,42 +97,187 @@ def gemm(*, M: int, N: int, K: int, ab_dtype: int, c_dtype: int,
         d.n_bias = len(bias_tab)
     d.relu = int(relu)
     d.aux = aux.data_ptr() if aux is not None else None
-    if splits is None:
-        splits = auto_splits(M, N, K, batch0 * batch1, ab_dtype)
-    d.splits = splits
-    ws = None
     if dbias_tab:
         for i, t in enumerate(dbias_tab):
             d.dbias_tab[i] = t.data_ptr() if t is not None else None
         d.n_dbias = len(dbias_tab)
         d.dbias_acc = int(dbias_acc)
-    if splits > 1:
-        nbytes = _lib.load().jmt_gemm_workspace_bytes(M, N, batch0 * batch1, splits)
-        if dbias_tab:
-            # the A row sums' split partials after the slabs (16-B aligned: the slab bytes are)
-            dbytes = splits * batch0 * M * 4
-            ws = workspace(nbytes + dbytes, device)
-            d.dbias_ws = ws.data_ptr() + nbytes
-            d.dbias_ws_bytes = dbytes
+    fam = {(True, True): "gemm_NT", (True, False): "gemm_NN", (False, False): "gemm_TN",
+           (False, True): "gemm_TT"}[(bool(a_kmajor), bool(b_kmajor))]
+    info = {"family": fam, "ab_dtype": ab_dtype, "c_dtype": c_dtype,
+            "a_kmajor": bool(a_kmajor), "b_kmajor": bool(b_kmajor), "M": M, "N": N,
+            "K": K, "batch": batch0 * batch1, "beta": beta,
+            "dbias": bool(dbias_tab),
+            "flops": 2.0 * M * N * K * batch0 * batch1,
+            "bytes": batch0 * batch1 * ((M + N) * K * (4 if ab_dtype == F32 else 2) +
+                                        M * N * (4 if c_dtype == F32 else 2)),
+            "inplace": any(p in list(c) for p in list(a) + list(b))}
+
+    def single():
+        sp = splits if splits is not None else auto_splits(M, N, K, batch0 * batch1, ab_dtype)
+        d.splits = sp
+        ws = None
+        if sp > 1:
+            nbytes = _lib.load().jmt_gemm_workspace_bytes(M, N, batch0 * batch1, sp)
+            if dbias_tab:
+                # the A row sums' split partials after the slabs (16-B aligned: the slab bytes are)
+                dbytes = sp * batch0 * M * 4
+                ws = workspace(nbytes + dbytes, device)
+                d.dbias_ws = ws.data_ptr() + nbytes
+                d.dbias_ws_bytes = dbytes
+            else:
+                ws = workspace(nbytes, device)
+            d.workspace = ws.data_ptr()
+            d.ws_bytes = nbytes
+        launch = lambda: _lib.check(_lib.load().jmt_gemm(C.byref(d), stream()), "jmt_gemm")
+        if _launch_hook is not None:
+            _launch_hook(info, launch)
         else:
-            ws = workspace(nbytes, device)
-        d.workspace = ws.data_ptr()
-        d.ws_bytes = nbytes
-    launch = lambda: _lib.check(_lib.load().jmt_gemm(C.byref(d), stream()), "jmt_gemm")
-    if _launch_hook is not None:
-        fam = {(True, True): "gemm_NT", (True, False): "gemm_NN", (False, False): "gemm_TN",
-               (False, True): "gemm_TT"}[(bool(a_kmajor), bool(b_kmajor))]
-        _launch_hook({"family": fam, "ab_dtype": ab_dtype, "c_dtype": c_dtype,
-                      "a_kmajor": bool(a_kmajor), "b_kmajor": bool(b_kmajor), "M": M, "N": N,
-                      "K": K, "batch": batch0 * batch1, "beta": beta,
-                      "dbias": bool(dbias_tab),
-                      "flops": 2.0 * M * N * K * batch0 * batch1,
-                      "bytes": batch0 * batch1 * ((M + N) * K * (4 if ab_dtype == F32 else 2) +
-                                                  M * N * (4 if c_dtype == F32 else 2)),
-                      "inplace": any(p in list(c) for p in list(a) + list(b))}, launch)
-    else:
-        launch()
-    return ws   # keep alive until the launch is ordered (caching allocator is stream-ordered)
+            launch()
+        return ws   # keep alive until the launch is ordered (caching allocator is stream-ordered)
+
+    if done is not None and splits is None and _wgrad_enqueue(
+            _WgradEntry(d, info, single, done, tuple(keep), device), defer):
+        return None
+    ws = single()
+    if done is not None:
+        done()
+    return ws
+
+
+# ------------------------------------------------------------------ grouped weight gradients
+# The step's weight gradients are few 256 x 256 tiles over a long K each: launched one by one,
+# every launch spreads its tiles over a full grid of split-K items and pays a slab set and a
+# reduce launch of its own.  Launches that sit next to each other are queued instead and flushed
+# as ONE jmt_gemm_grouped launch (+ one reduce).  JMT_WGRAD_GROUP=0: every launch as before.
+_wgrad_group = {"on": os.environ.get("JMT_WGRAD_GROUP", "1") != "0"}
+
+
+def wgrad_group_enabled() -> bool:
+    return _wgrad_group["on"]
+
+
+class _WgradEntry:
+    __slots__ = ("d", "info", "single", "done", "keep", "device", "stream")
+
+    def __init__(self, d, info, single, done, keep, device):
+        self.d, self.info, self.single, self.done = d, info, single, done
+        self.keep, self.device = keep, device
+        self.stream = torch.cuda.current_stream()
+
+
+_wq = {"depth": 0, "scoped": [], "deferred": [], "task": None}
+
+
+def _wgrad_enqueue(e: "_WgradEntry", defer: bool) -> bool:
+    if not _wgrad_group["on"]:
+        return False
+    if _wq["depth"] > 0:
+        _wq["scoped"].append(e)
+        return True
+    if not defer:
+        return False
+    task = torch._C._current_graph_task_id()
+    if task < 0:                        # outside a backward pass: nothing would flush it
+        return False
+    if _wq["task"] != task:             # (a backward that raised cannot leave stale entries)
+        _wq["deferred"].clear()
+        _wq["task"] = task
+
+        def _cb():
+            _wq["task"] = None
+            ents, _wq["deferred"] = _wq["deferred"], []
+            wgrad_flush(ents)
+
+        torch.autograd.Variable._execution_engine.queue_callback(_cb)
+    _wq["deferred"].append(e)
+    return True
+
+
+class wgrad_scope:
+    """Weight-gradient launches issued inside (ops.gemm with `done`) are flushed together at the
+    exit, on the stream current there: for launches that already sit next to each other."""
+
+    def __enter__(self):
+        _wq["depth"] += 1
+        return self
+
+    def __exit__(self, et, ev, tb):
+        _wq["depth"] -= 1
+        if _wq["depth"] == 0:
+            ents, _wq["scoped"] = _wq["scoped"], []
+            if et is None:
+                wgrad_flush(ents)
+        return False
+
+
+def wgrad_flush(entries) -> None:
+    """Launch the queued weight gradients on the current stream: those the grouped form takes
+    (jmt_gemm_grouped_plan says so per entry) as grouped launches of up to 16 problems, the rest
+    (the 128-row regressor gradient, fp32 compute, ...) through jmt_gemm as before; then report
+    every entry done."""
+    if not entries:
+        return
+    lib = _lib.load()
+    cur = torch.cuda.current_stream()
+    for st in {e.stream for e in entries}:
+        if st != cur:                   # operands written on a branch stream
+            cur.wait_stream(st)
+    groups, rest = [], []
+    for e in entries:
+        e.d.splits = 0
+        if lib.jmt_gemm_grouped_plan(C.byref(e.d), 1, None) != _lib.OK:
+            rest.append(e)
+            continue
+        key = (e.d.ab_dtype, e.d.a_kmajor, e.d.b_kmajor, e.device)
+        for g in groups:
+            if g[0] == key and len(g[1]) < 16 and \
+                    sum(x.d.n_a + x.d.n_b + x.d.n_c + x.d.n_dbias for x in g[1] + [e]) <= 216:
+                g[1].append(e)
+                break
+        else:
+            groups.append((key, [e]))
+    for _, ents in groups:
+        if len(ents) == 1:
+            rest.append(ents[0])
+            continue
+        n = len(ents)
+        arr = (GemmDesc * n)(*[e.d for e in ents])
+        nbytes = lib.jmt_gemm_grouped_workspace_bytes(arr, n)
+        ws = workspace(nbytes, ents[0].device)
+        launch = lambda: _lib.check(lib.jmt_gemm_grouped(arr, n, ws.data_ptr(), nbytes, stream()),
+                                    "jmt_gemm_grouped")
+        if _launch_hook is not None:
+            info = dict(ents[0].info, grouped=n,
+                        flops=sum(e.info["flops"] for e in ents),
+                        bytes=sum(e.info["bytes"] for e in ents),
+                        dbias=any(e.info["dbias"] for e in ents))
+            _launch_hook(info, launch)
+        else:
+            launch()
+    for e in rest:
+        e.single()
+    for e in entries:
+        e.done()
+        if e.stream != cur:
+            for t in e.keep:
+                if isinstance(t, torch.Tensor) and t.is_cuda:
+                    t.record_stream(cur)
+
+
+def gemm_grouped(descs, device, splits_out=None):
+    """jmt_gemm_grouped on GemmDesc structures (tests, probes): returns the workspace."""
+    lib = _lib.load()
+    n = len(descs)
+    arr = (GemmDesc * n)(*descs)
+    if splits_out is not None:
+        sp = (C.c_int * n)()
+        _lib.check(lib.jmt_gemm_grouped_plan(arr, n, sp), "jmt_gemm_grouped_plan")
+        splits_out[:] = list(sp)
+    nbytes = lib.jmt_gemm_grouped_workspace_bytes(arr, n)
+    ws = workspace(nbytes, device)
+    _lib.check(lib.jmt_gemm_grouped(arr, n, ws.data_ptr(), nbytes, stream()), "jmt_gemm_grouped")
+    return ws
 
 
 # ------------------------------------------------------------------------------------ rows

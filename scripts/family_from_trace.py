@@ -27,9 +27,21 @@ DEMANGLED = re.compile(r"gemm_(?:persist3?_|pp_split_|pp2?_)?kernel<.*?(true|fal
 BROKEN_PERSIST = re.compile(r"gemm_(?:persist3?|pp2?)_kernel<bool _Accum, bool, E, (true|false),")
 # the split-K ping-pong kernel (cfg 44) takes the weight gradients (A MN-major): B decides too
 BROKEN_SPLIT = re.compile(r"gemm_pp_split_kernel<bool _Accum, bool, E, (true|false),")
+# the grouped weight-gradient kernel (jmt_gemm_grouped) and its reduce (group_reduce_kernel)
+BROKEN_GROUP = re.compile(r"gemm_group_kernel<bool _Accum, bool, E, (true|false),")
+MANGLED_GROUP = re.compile(r"gemm_group_kernel.*?Lb([01])ELb([01])E")
 
 
 def family(name: str):
+    if "gemm_group_kernel" in name:      # grouped weight gradients: MN-major A and B in the step
+        bs = BROKEN_GROUP.search(name)
+        if bs:
+            return "gemm_TT" if bs.group(1) == "true" else "gemm_TN"
+        m = MANGLED_GROUP.search(name)
+        if m:
+            return {("1", "1"): "gemm_NT", ("1", "0"): "gemm_NN", ("0", "0"): "gemm_TN",
+                    ("0", "1"): "gemm_TT"}[(m.group(1), m.group(2))]
+        return "gemm_TN"
     if "gemm_kernel" in name or "gemm_persist" in name or "gemm_pp" in name:
         bs = BROKEN_SPLIT.search(name)
         if bs:
@@ -47,7 +59,7 @@ def family(name: str):
             ak, bk = m.group(1) == "true", m.group(2) == "true"
         return {(True, True): "gemm_NT", (True, False): "gemm_NN", (False, False): "gemm_TN",
                 (False, True): "gemm_TT"}[(ak, bk)]
-    if "splitk_reduce" in name:
+    if "splitk_reduce" in name or "group_reduce" in name:
         return "reduce"
     if "small_attn_fwd" in name:
         return "small_attn_fwd"
