@@ -242,7 +242,13 @@ int jmt_attn_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* go, i
  * ABI 7: when dq != NULL also dQ = dS K (k: the attention's K operand, a view like q; dq like
  * dk, rows Lq), as 128-query items beside the 128-key dK / dV items of the same launch, and P /
  * dS are read in the tile-major layout jmt_attn_bwd(dq = NULL) writes (the pair's contract);
- * dS keys [0, 32 ceil(Lk / 32)) feed dQ. */
+ * dS keys [0, 32 ceil(Lk / 32)) feed dQ; ldp a multiple of 32.
+ * With dq != NULL a launch works in items of 128 or of 160 rows (bitwise the same results; 160
+ * where it pads fewer rows per head and the dK / dV / dQ row strides keep 160 rows inside
+ * 32-bit offsets).  ldp is 128 ceil(Lk / 128) either way.  jmt_attn_dkdv_plan returns the tile
+ * (128 or 160) jmt_attn_dkdv takes for these sizes and row strides; no GPU call. */
+int jmt_attn_dkdv_plan(int Lq, int Lk, int H, int64_t sdk_l, int64_t sdv_l, int64_t sdq_l,
+                       int has_dq);
 int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const void* p, const void* ds,
                   int64_t ldp, const void* go, int64_t sgo_l, int64_t sgo_n, const void* q,
                   int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n, void* dk,

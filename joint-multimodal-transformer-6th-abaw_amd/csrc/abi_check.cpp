@@ -162,6 +162,17 @@ int main() {
                                                       384, algn, 512, 512, algn, 512, 512, misal,
                                                       512, 512, algn, 512, 512, algn, 512, 512,
                                                       misal, 512, 512, nullptr));
+  // tile-major P / dS (dq != NULL): ldp covers 128-key tiles but is no multiple of 32
+  expect_err("attn_dkdv dq ldp % 32", jmt_attn_dkdv(JMT_BF16, 2, 1, 300, 300, 512, algn, algn,
+                                                    392, algn, 512, 512, algn, 512, 512, algn,
+                                                    512, 512, algn, 512, 512, algn, 512, 512,
+                                                    algn, 512, 512, nullptr));
+  if (jmt_attn_dkdv_plan(300, 300, 1, 512, 512, 512, 1) != 160 ||
+      jmt_attn_dkdv_plan(300, 300, 1, 512, 512, 512, 0) != 128 ||
+      jmt_attn_dkdv_plan(256, 256, 1, 512, 512, 512, 1) != 128) {
+    fprintf(stderr, "FAIL attn_dkdv_plan\n");
+    ++g_fail;
+  }
   expect_err("attn_bwd pds ldp", jmt_attn_bwd(JMT_BF16, 2, 1, 300, 300, 512, algn, 512, 512,
                                               algn, 512, 512, algn, 512, 512, algn, 512, 512,
                                               algn, 512, 512, fnull, algn, algn, 300, nullptr,

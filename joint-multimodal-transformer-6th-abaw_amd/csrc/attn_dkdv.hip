@@ -28,24 +28,66 @@
 //    and the waits that follow count them).
 // HBM bytes per (n, h): Lq rows of dO and of Q (1 KiB each; once per head when its key tiles share
 // the L2), Lq x 128 ceil(Lk / 128) x 2 B of P and of dS, Lk rows of dK and of dV written.
+//
+// Two tiles (template parameter NKG = 16-row groups per item; one instantiation serves the three
+// roles of a launch; jmt_attn_dkdv_plan picks per launch):
+//  * NKG = 8, the geometry above: 128 rows, 40 KiB stages x 4.
+//  * NKG = 10: 160 rows, so L = 300 is two items per product instead of three (6 % padded rows
+//    instead of 28 %).  Accumulator 160 registers; the P / dS fragments are read and consumed in
+//    two batches of five and the lane bases of the transposed reads are formed by an XOR in front
+//    of each read, the row DMA takes a scalar base (glds16_sv): 227 VGPRs, no spills.  The P / dS
+//    image is five [32 queries][32 keys] sub-images of 64-B rows (the hand-off's 32-key tiles as
+//    they are; chunk c of row r at c ^ 2 in rows 4-7 of every 8: simg_off), the dQ role's dS image
+//    160 queries x 32 keys (qimg_off): 42 KiB stages x 3.  Sub-tiles past ldp / 32 (ldp stays
+//    128 ceil(Lk / 128): Lk = 130 has 256 columns, the item 320) are clamped to the head's last
+//    one; they feed keys past Lk only.  Tile-major P / dS only (dq != NULL).
+//  Each output element is contracted over the same 32-deep chunks in the same order by both, so
+//  the results are bitwise equal.
+//
+// vmcnt accounting.  Every wait in the chunk loop is s_waitcnt vmcnt(S NDMA + B NST) with
+// immediate operands: S later stages and B items' output stores stay in flight behind the
+// awaited stage.  This is exact only if EVERY wave issues the same NDMA DMA wave-instructions per
+// stage and the same NST stores per item; a count larger than what a wave really issued
+// under-waits (the stage is read before it landed), a smaller one only waits longer.  Hence:
+//  * stores are never skipped per wave (the buffer range check drops rows instead): NST = 2 NKG;
+//  * the 10 KiB P / dS image of NKG = 10 is ten 1-KiB wave-instructions' worth, which do not deal
+//    over 8 waves: each wave issues TWO instructions of 40 active lanes (640 B each; the LDS
+//    address is base + 16 lane, so the inactive lanes leave their bytes to the next piece),
+//    NDMA = 4 + 2 = 6 for every wave; NKG = 8: 4 + 1 = 5 of 64 lanes;
+//  * the largest count, (NS - 2) NDMA + (NS - 1) NST, must fit vmcnt's 6 bits (static_assert).
 #include "attn_common.h"
 
 namespace jmt {
 
-constexpr int DK_KT = 128;                              // keys per item
-constexpr int DK_QC = 32;                               // queries per chunk (one MFMA k-step)
-constexpr int DK_PROW = 2 * DK_KT;                      // P / dS image row bytes
-constexpr int DK_IMG = DK_QC * AT_ROWB;                 // dO or Q image (32 KiB)
-constexpr int DK_PIMG = DK_QC * DK_PROW;                // P or dS image (8 KiB)
-constexpr int DK_STAGE = DK_IMG + DK_PIMG;              // 40 KiB
+constexpr int DK_QC = 32;                               // contraction rows per chunk (one k-step)
+constexpr int DK_IMG = DK_QC * AT_ROWB;                 // dO / Q / K row image (32 KiB)
 #ifndef JMT_DKDV_NS
 #define JMT_DKDV_NS 4                                   // (dev A/B: 3 -> 120 KiB)
 #endif
-constexpr int DK_NS = JMT_DKDV_NS;                      // stages
-constexpr int DK_LDS = DK_NS * DK_STAGE;                // 160 KiB
-static_assert(DK_NS >= 2 && DK_NS <= 4, "2-4 stages (the wait table covers 0-2 later stages)");
-constexpr int DK_NDMA = DK_QC / 8 + 1;                  // DMA wave-instructions per wave per stage
-constexpr int DK_NST = 16;                              // output stores per wave per item
+
+// Tile geometry, NKG = 16-row groups per item: 8 (128 rows) or 10 (160 rows)
+template <int NKG>
+struct DkGeo {
+  static constexpr int KT = 16 * NKG;                   // output rows per item
+  static constexpr int PROW = 2 * KT;                   // P / dS image row bytes (128-row form)
+  static constexpr int PIMG = DK_QC * PROW;             // P or dS image (8 / 10 KiB)
+  static constexpr int STAGE = DK_IMG + PIMG;           // 40 / 42 KiB
+  static constexpr int NS = NKG == 8 ? JMT_DKDV_NS : 3; // stages
+  static constexpr int LDS = NS * STAGE;                // 160 / 126 KiB
+  // the P / dS image is PIMG / 1024 wave-instructions' worth of bytes, dealt as NPD per wave of
+  // PLANES active lanes each (8 x 1 x 64 lanes, or 8 x 2 x 40 lanes), so that EVERY wave issues
+  // the same NDMA per stage
+  static constexpr int NPD = (PIMG / 1024 + 7) / 8;
+  static constexpr int PLANES = PIMG / 16 / 8 / NPD;
+  static constexpr int NDMA = DK_QC / 8 + NPD;          // DMA wave-instructions per wave per stage
+  static constexpr int NST = 2 * NKG;                   // output stores per wave per item
+  static_assert(NKG == 8 || NKG == 10, "128- or 160-row items");
+  static_assert(NS >= 2 && NS <= 4, "2-4 stages (the wait table covers 0-2 later stages)");
+  static_assert(LDS <= 160 * 1024, "stages exceed the LDS");
+  static_assert(8 * NPD * PLANES * 16 == PIMG && PLANES <= 64, "P / dS DMA split");
+  // the largest count the chunk loop waits on: NS - 2 later stages, NS - 1 items' stores
+  static_assert((NS - 2) * NDMA + (NS - 1) * NST < 64, "vmcnt range");
+};
 
 struct AttnDkdvArgs {
   const void* p;
@@ -60,12 +102,21 @@ struct AttnDkdvArgs {
   int Lq, Lk, H, nkt, nqd, ipn, nitems;
 };
 
-// byte offset of 16-B chunk `c` of row `r` of a P / dS image
+// byte offset of 16-B chunk `c` of row `r` of the P / dS image of a 128-key item (256-B rows)
 __device__ __forceinline__ int pimg_off(int r, int c) {
-  return r * DK_PROW + ((c ^ ((r & 7) << 1)) << 4);
+  return r * DkGeo<8>::PROW + ((c ^ ((r & 7) << 1)) << 4);
 }
 
-// byte offset of 16-B chunk `c` of row `r` of a dS image of the dQ product (128 query rows x 32
+// byte offset of 16-B chunk `c` of row `r` of one [32 queries][32 keys] sub-image (64-B rows) of
+// the P / dS image of a 160-key item (five sub-images, one per 32-key tile of the hand-off):
+// chunk c ^ 2 in rows 4-7 of every 8.  A 32-lane half of a ds_read_b64_tr_b16 takes 32 B of each
+// of 8 consecutive rows: rows 0-3 and 4-7 then sit in opposite 128-B halves of the 256 B of banks
+// (conflict-free); the XOR leaves the order of the two chunks of those 32 B alone.
+__device__ __forceinline__ int simg_off(int r, int c) {
+  return r * 64 + ((c ^ ((r >> 1) & 2)) << 4);
+}
+
+// byte offset of 16-B chunk `c` of row `r` of a dS image of the dQ product (KT query rows x 32
 // keys, 64-B rows): chunk c ^ ((r >> 2) & 3), so the two ds_read_b64 of a fragment (rows li of a
 // 16-row group, keys 4 g and 16 + 4 g) are conflict-free
 __device__ __forceinline__ int qimg_off(int r, int c) {
@@ -73,22 +124,23 @@ __device__ __forceinline__ int qimg_off(int r, int c) {
 }
 
 // item -> (n H + h, n, h, product (0: dV, 1: dK, 2: dQ), first key (0, 1) or query (2), chunks).
-// Per (n, h): nkt dV items, nkt dK items (128-key tiles, the contraction over queries in 32-row
-// chunks), then nqd dQ items (128-query tiles, the contraction over keys in 32-key chunks).
+// Per (n, h): nkt dV items, nkt dK items (KT-key tiles, the contraction over queries in 32-row
+// chunks), then nqd dQ items (KT-query tiles, the contraction over keys in 32-key chunks).
 struct DkItem {
   int nh, n, hd, role, k0, nch;
 };
+template <int KT>
 __device__ __forceinline__ DkItem dk_decode(const AttnDkdvArgs& a, int it) {
   DkItem d;
   d.nh = it / a.ipn;
   const int r = it - d.nh * a.ipn;
   if (r < 2 * a.nkt) {
     d.role = r >= a.nkt;
-    d.k0 = (r - d.role * a.nkt) * DK_KT;
+    d.k0 = (r - d.role * a.nkt) * KT;
     d.nch = (a.Lq + DK_QC - 1) / DK_QC;
   } else {
     d.role = 2;
-    d.k0 = (r - 2 * a.nkt) * DK_KT;
+    d.k0 = (r - 2 * a.nkt) * KT;
     d.nch = (a.Lk + DK_QC - 1) / DK_QC;
   }
   d.n = d.nh / a.H;
@@ -96,10 +148,10 @@ __device__ __forceinline__ DkItem dk_decode(const AttnDkdvArgs& a, int it) {
   return d;
 }
 
-// one stage: rows q0 .. q0+31 (clamped to Lq - 1) of dO or Q, and of the P or dS tile (keys
-// k0 .. k0+127): 4 + 1 DMA wave-instructions per wave.  Row offsets in 32-bit byte arithmetic
-// from a per-head base (the host checks Lq rows fit): the 64-bit row products of stage_rows cost
-// ~25 scalar instructions per DMA, and the CU's one scalar unit serves all 8 waves.
+// one stage of a 128-row item: rows q0 .. q0+31 (clamped to Lq - 1) of dO or Q, and of the P or dS
+// tile (keys k0 .. k0+127): 4 + 1 DMA wave-instructions per wave.  Row offsets in 32-bit byte
+// arithmetic from a per-head base (the host checks Lq rows fit): the 64-bit row products of
+// stage_rows cost ~25 scalar instructions per DMA, and the CU's one scalar unit serves all 8 waves.
 template <typename T>
 __device__ __forceinline__ void dkdv_stage(char* st, const AttnDkdvArgs& a, const DkItem& d,
                                            int q0) {
@@ -161,28 +213,106 @@ __device__ __forceinline__ void dkdv_stage(char* st, const AttnDkdvArgs& a, cons
              st + DK_IMG + wu * 1024);
 }
 
-// s_waitcnt vmcnt(stages * DK_NDMA + stores * DK_NST) for the counts the chunk loop meets:
-// 0-2 later stages and 0-3 items' output stores in flight behind the awaited stage
-template <int S>
-__device__ __forceinline__ void dkdv_wait_s(int stores) {
-  switch (stores) {
-    case 0: wait_vmcnt<S * DK_NDMA>(); break;
-    case 1: wait_vmcnt<S * DK_NDMA + DK_NST>(); break;
-    case 2: wait_vmcnt<S * DK_NDMA + 2 * DK_NST>(); break;
-    default: wait_vmcnt<S * DK_NDMA + 3 * DK_NST>(); break;
+// one stage of a 160-row item (tile-major P / dS only): the 32 rows as above (scalar row base +
+// lane offset), and the 10 KiB P / dS image as two wave-instructions of 40 active lanes per wave
+// (wave w, instruction j: image bytes 640 (2 w + j) .. +639).  dV / dK: five [32 queries][32 keys]
+// sub-images (simg_off), sub-image s from hand-off tile k0 / 32 + s, clamped to the last tile of
+// the head's region (ldp / 32 - 1: ldp covers 128-key tiles only, and the tile after belongs to
+// the next head; a clamped tile feeds keys past Lk, which are not stored).  dQ: 160 queries x the
+// chunk's 32 keys (qimg_off), from hand-off tile q0 / 32.
+template <typename T>
+__device__ __forceinline__ void dkdv_stage160(uint32_t st, const AttnDkdvArgs& a, const DkItem& d,
+                                              int q0) {
+  typedef DkGeo<10> G;
+  const int lane = threadIdx.x & 63;
+  const int wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const char* rb;
+  int ldb, clen;
+  if (d.role == 0) {
+    rb = (const char*)((const T*)a.go + (int64_t)d.n * a.sgo_n + d.hd * AT_DH);
+    ldb = (int)(a.sgo_l * (int64_t)sizeof(T));
+    clen = a.Lq;
+  } else if (d.role == 1) {
+    rb = (const char*)((const T*)a.q + (int64_t)d.n * a.sq_n + d.hd * AT_DH);
+    ldb = (int)(a.sq_l * (int64_t)sizeof(T));
+    clen = a.Lq;
+  } else {
+    rb = (const char*)((const T*)a.k + (int64_t)d.n * a.sk_n + d.hd * AT_DH);
+    ldb = (int)(a.sk_l * (int64_t)sizeof(T));
+    clen = a.Lk;
+  }
+#pragma unroll
+  for (int i = 0; i < DK_QC / 8; ++i) {
+    const int r = wu * (DK_QC / 8) + i;
+    const int src = min(q0 + r, clen - 1);
+    JMT_DCHECK(src >= 0 && src < clen);
+    const unsigned off = (unsigned)(lane ^ ((r & 7) << 1)) << 4;
+    glds16_sv(rb + (unsigned)(src * ldb), off, st + r * AT_ROWB);
+  }
+  const char* pb = (const char*)((const T*)(d.role == 0 ? a.p : a.ds) +
+                                 (int64_t)d.nh * a.Lq * a.ldp);
+  const int ntile = (int)(a.ldp >> 5);                  // 32-key tiles of the head's region
+  if (lane < G::PLANES) {
+#pragma unroll
+    for (int j = 0; j < G::NPD; ++j) {
+      const int b0 = (wu * G::NPD + j) * (16 * G::PLANES);
+      const int b = b0 + 16 * lane;                     // image byte of this lane's 16 B
+      const int pc = (b >> 4) & 3;                      // physical chunk of its 64-B row
+      int tile, row, c;
+      if (d.role == 2) {
+        const int r = b >> 6;                           // dS image row (query d.k0 + r)
+        c = pc ^ ((r >> 2) & 3);
+        tile = q0 >> 5;
+        row = min(d.k0 + r, a.Lq - 1);
+      } else {
+        const int r = (b >> 6) & 31;                    // sub-image row (query q0 + r)
+        c = pc ^ ((r >> 1) & 2);
+        tile = min((d.k0 >> 5) + (b >> 11), ntile - 1);
+        row = min(q0 + r, a.Lq - 1);
+      }
+      JMT_DCHECK(row >= 0 && tile >= 0 && tile < ntile);
+      glds16_sv(pb, (unsigned)((tile * a.Lq + row) * 64 + 16 * c), st + DK_IMG + b0);
+    }
   }
 }
+
+// s_waitcnt vmcnt(stages * NDMA + stores * NST) for the counts the chunk loop meets: 0 .. NS - 2
+// later stages and 0 .. NS - 1 items' output stores in flight behind the awaited stage
+template <int NKG, int S>
+__device__ __forceinline__ void dkdv_wait_s(int stores) {
+  typedef DkGeo<NKG> G;
+  if constexpr (S <= G::NS - 2) {
+    if (stores == 0) wait_vmcnt<S * G::NDMA>();
+    else if (stores == 1 || G::NS == 2) wait_vmcnt<S * G::NDMA + G::NST>();
+    else if constexpr (G::NS >= 3) {
+      if (stores == 2 || G::NS == 3) wait_vmcnt<S * G::NDMA + 2 * G::NST>();
+      else if constexpr (G::NS >= 4) wait_vmcnt<S * G::NDMA + 3 * G::NST>();
+    }
+  } else {
+    wait_vmcnt<0>();
+  }
+}
+template <int NKG>
 __device__ __forceinline__ void dkdv_wait(int stages, int stores) {
-  if (stages == 0) dkdv_wait_s<0>(stores);
-  else if (stages == 1) dkdv_wait_s<1>(stores);
-  else dkdv_wait_s<2>(stores);
+  if (stages == 0) dkdv_wait_s<NKG, 0>(stores);
+  else if (stages == 1) dkdv_wait_s<NKG, 1>(stores);
+  else dkdv_wait_s<NKG, 2>(stores);
 }
 
-template <typename T>
+// Between the dS fragment reads of the dQ role: keeps hipcc from pairing two ds_read_b64 (rows 16
+// apart, or the two key halves) into one ds_read2st64_b64, which banks modulo 32 dwords and takes
+// 16 LDS cycles for what two ds_read_b64 do in 4: SQ_LDS_BANK_CONFLICT 27 % of SQ_LDS_IDX_ACTIVE
+// with the paired reads, 0 without, and 40 % fewer active LDS cycles (profiles/r09/dkdv_pmc*.txt).
+#define DK_NO_MERGE() asm volatile("" ::: "memory")
+
+template <typename T, int NKG>
 __global__ __launch_bounds__(512, 2) void attn_dkdv_kernel(AttnDkdvArgs a) {
   typedef typename Frag16<T>::t F;
   typedef typename Frag16<T>::h Hf;
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  typedef DkGeo<NKG> G;
+  constexpr int KT = G::KT, NS = G::NS, STAGE = G::STAGE;
+  constexpr int KB = NKG == 8 ? 8 : 5;                  // P / dS fragments read per batch
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = lane >> 4, li = lane & 15;
@@ -190,96 +320,137 @@ __global__ __launch_bounds__(512, 2) void attn_dkdv_kernel(AttnDkdvArgs a) {
   item_range(a.nitems, item, iend, istride);
   if (item >= iend) return;
 
-  int tb[4], pb[8];                                     // transposed-read lane bases
+  // transposed-read lane bases.  128 rows: one register per read, tb[t] and pb[kg].  160 rows:
+  // tb[t] = tb[0] ^ (t << 5) (the swizzle XOR and t sit in the same chunk bits) and the P / dS
+  // read of key group kg at (pb[0] ^ ((kg & 1) << 5)) + 2048 (kg >> 1), formed in front of the
+  // reads: the accumulator leaves no registers for 12 bases.
+  int tb[NKG == 8 ? 4 : 1], pb[NKG == 8 ? 8 : 1];
+  if constexpr (NKG == 8) {
 #pragma unroll
-  for (int t = 0; t < 4; ++t) tb[t] = tr_base(4 * (w & 1) + t, li, g, 0) + 256 * (w >> 1);
+    for (int t = 0; t < 4; ++t) tb[t] = tr_base(4 * (w & 1) + t, li, g, 0) + 256 * (w >> 1);
 #pragma unroll
-  for (int kg = 0; kg < 8; ++kg)
-    pb[kg] = pimg_off(4 * g + (li >> 2), 2 * kg + ((li & 3) >> 1)) + 8 * (li & 1);
+    for (int kg = 0; kg < 8; ++kg)
+      pb[kg] = pimg_off(4 * g + (li >> 2), 2 * kg + ((li & 3) >> 1)) + 8 * (li & 1);
+  } else {
+    tb[0] = tr_base(4 * (w & 1), li, g, 0) + 256 * (w >> 1);
+    pb[0] = simg_off(4 * g + (li >> 2), (li & 3) >> 1) + 8 * (li & 1);
+  }
+  auto lane_base = [](int base, int bits) __attribute__((always_inline)) {
+#if !defined(__OPTIMIZE__)
+    return base ^ bits;
+#else
+    int r;
+    asm volatile("v_xor_b32 %0, %2, %1" : "=v"(r) : "v"(base), "i"(bits));
+    return r;
+#endif
+  };
   // dQ: dS fragment of query group qg = rows 16 qg + li, keys 4 g .. +3 (k-slots 0-3) and
   // 16 + 4 g .. +3 (k-slots 4-7): the k-slot order of the transposed K-row reads
   const int qb0 = qimg_off(li, g >> 1) + 8 * (g & 1);
-  const int qb1 = qimg_off(li, 2 + (g >> 1)) + 8 * (g & 1);
+  const int qb1 = NKG == 8 ? qimg_off(li, 2 + (g >> 1)) + 8 * (g & 1) : 0;   // 160: qb0 ^ 32
+  const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
-  // issue cursor: the chunk whose stage goes out next (runs DK_NS - 1 chunks ahead of the compute)
+  // issue cursor: the chunk whose stage goes out next (runs NS - 1 chunks ahead of the compute)
   int is_item = item, is_c = 0;
-  DkItem is_d = dk_decode(a, item);
+  DkItem is_d = dk_decode<KT>(a, item);
   bool is_ok = true;
   int is_buf = 0;
   unsigned after = 0;      // 4 bits per buffer: store batches issued after the stage it holds
   int inflight = 0;        // stages issued and not yet waited for
   auto issue = [&]() {
     if (is_ok) {
-      dkdv_stage<T>(smem + is_buf * DK_STAGE, a, is_d, DK_QC * is_c);
+      if constexpr (NKG == 8) dkdv_stage<T>(smem + is_buf * STAGE, a, is_d, DK_QC * is_c);
+      else dkdv_stage160<T>(lbase + is_buf * STAGE, a, is_d, DK_QC * is_c);
       after &= ~(15u << (4 * is_buf));
       ++inflight;
       if (++is_c == is_d.nch) {
         is_c = 0;
         is_item += istride;
         is_ok = is_item < iend;
-        if (is_ok) is_d = dk_decode(a, is_item);
+        if (is_ok) is_d = dk_decode<KT>(a, is_item);
       }
     }
-    is_buf = is_buf == DK_NS - 1 ? 0 : is_buf + 1;
+    is_buf = is_buf == NS - 1 ? 0 : is_buf + 1;
   };
-  for (int i = 0; i < DK_NS - 1; ++i) issue();
+  for (int i = 0; i < NS - 1; ++i) issue();
   int buf = 0;
 
   while (true) {
-    const DkItem d = dk_decode(a, item);
+    const DkItem d = dk_decode<KT>(a, item);
     const bool more = item + istride < iend;
-    f32x4 acc[8][4];
+    f32x4 acc[NKG][4];
 #pragma unroll
-    for (int kg = 0; kg < 8; ++kg)
+    for (int kg = 0; kg < NKG; ++kg)
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc[kg][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int c = 0; c < d.nch; ++c) {
-      const char* cur = smem + buf * DK_STAGE;
+      const char* cur = smem + buf * STAGE;
       // this chunk's stage landed (the later stages and the output stores issued after it may
       // stay in flight), and every wave is done reading the buffer restaged below
-      dkdv_wait(inflight - 1, (after >> (4 * buf)) & 15);
+      dkdv_wait<NKG>(inflight - 1, (after >> (4 * buf)) & 15);
       --inflight;
       lds_barrier();
       issue();
-      F kf[8];
       const int c0 = DK_QC * c;                         // first contraction index of the chunk
       const int clen = d.role == 2 ? a.Lk : a.Lq;       // contraction length
-      if (d.role != 2) {
-#pragma unroll
-        for (int kg = 0; kg < 8; ++kg) {
-          const Hf lo = tr_read<Hf>(cur + DK_IMG + pb[kg]);
-          const Hf hi = tr_read<Hf>(cur + DK_IMG + pb[kg] + 16 * DK_PROW);
-          kf[kg] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-      } else {
-#pragma unroll
-        for (int qg = 0; qg < 8; ++qg) {
-          const Hf lo = *(const Hf*)(cur + DK_IMG + qb0 + 1024 * qg);
-          const Hf hi = *(const Hf*)(cur + DK_IMG + qb1 + 1024 * qg);
-          kf[qg] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-      }
-      if (c0 + DK_QC > clen) {   // k-slot e holds contraction index c0 + 16 (e >> 2) + 4 g + (e & 3)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const bool in = c0 + 16 * (e >> 2) + 4 * g + (e & 3) < clen;
-#pragma unroll
-          for (int kg = 0; kg < 8; ++kg) kf[kg][e] = in ? kf[kg][e] : from_f<T>(0.f);
-        }
-      }
       F df[4];
+      // the P / dS fragments in batches of KB groups (128 rows: one batch, read before the dO /
+      // Q / K fragments; 160 rows: two of five, 20 registers live instead of 40)
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const Hf lo = tr_read<Hf>(cur + tb[t]);
-        const Hf hi = tr_read<Hf>(cur + tb[t] + 16 * AT_ROWB);
-        df[t] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      for (int k0 = 0; k0 < NKG; k0 += KB) {
+        F kf[KB];
+        if (d.role != 2) {
+#pragma unroll
+          for (int j = 0; j < KB; ++j) {
+            const int kg = k0 + j;
+            const char* pa;
+            if constexpr (NKG == 8) pa = cur + DK_IMG + pb[kg];
+            else pa = cur + DK_IMG + lane_base(pb[0], (kg & 1) << 5) + 2048 * (kg >> 1);
+            const Hf lo = tr_read<Hf>(pa);
+            const Hf hi = tr_read<Hf>(pa + (NKG == 8 ? 16 * G::PROW : 16 * 64));
+            kf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+          }
+        } else {
+          const char* qa0 = cur + DK_IMG + qb0;
+          const char* qa1;
+          if constexpr (NKG == 8) qa1 = cur + DK_IMG + qb1;
+          else qa1 = cur + DK_IMG + lane_base(qb0, 32);
+#pragma unroll
+          for (int j = 0; j < KB; ++j) {
+            const Hf lo = *(const Hf*)(qa0 + 1024 * (k0 + j));
+            DK_NO_MERGE();
+            const Hf hi = *(const Hf*)(qa1 + 1024 * (k0 + j));
+            DK_NO_MERGE();
+            kf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+          }
+        }
+        // k-slot e holds contraction index c0 + 16 (e >> 2) + 4 g + (e & 3)
+        if (c0 + DK_QC > clen) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const bool in = c0 + 16 * (e >> 2) + 4 * g + (e & 3) < clen;
+#pragma unroll
+            for (int j = 0; j < KB; ++j) kf[j][e] = in ? kf[j][e] : from_f<T>(0.f);
+          }
+        }
+        if (k0 == 0) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const char* ta;
+            if constexpr (NKG == 8) ta = cur + tb[t];
+            else ta = cur + lane_base(tb[0], t << 5);
+            const Hf lo = tr_read<Hf>(ta);
+            const Hf hi = tr_read<Hf>(ta + 16 * AT_ROWB);
+            df[t] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int j = 0; j < KB; ++j) acc[k0 + j][t] = mfma16(df[t], kf[j], acc[k0 + j][t]);
       }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int kg = 0; kg < 8; ++kg) acc[kg][t] = mfma16(df[t], kf[kg], acc[kg][t]);
-      buf = buf == DK_NS - 1 ? 0 : buf + 1;
+      buf = buf == NS - 1 ? 0 : buf + 1;
     }
 
     // ---- outputs: lane = key (dQ: query) k0 + 16 kg + li, dims 64 w + 16 t + 4 g + r; subtiles
@@ -293,13 +464,13 @@ __global__ __launch_bounds__(512, 2) void attn_dkdv_kernel(AttnDkdvArgs a) {
       const uint64_t ba = (uint64_t)(uintptr_t)ob;
       const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)ba);
       const uint32_t bhi = __builtin_amdgcn_readfirstlane((uint32_t)(ba >> 32));
-      const int nrows = min(DK_KT, (d.role == 2 ? a.Lq : a.Lk) - d.k0);
+      const int nrows = min(KT, (d.role == 2 ? a.Lq : a.Lk) - d.k0);
       const int bytes = __builtin_amdgcn_readfirstlane((int)(nrows * sl * (int64_t)sizeof(T)));
       const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(
           (void*)(((uint64_t)bhi << 32) | blo), 0, bytes, 0x00020000);
       const int sl32 = (int)sl;
 #pragma unroll
-      for (int kg = 0; kg < 8; ++kg) {
+      for (int kg = 0; kg < NKG; ++kg) {
 #pragma unroll
         for (int jp = 0; jp < 2; ++jp) {
           uint32_t pk[2][2];
@@ -320,7 +491,7 @@ __global__ __launch_bounds__(512, 2) void attn_dkdv_kernel(AttnDkdvArgs a) {
         }
       }
     }
-    // these stores follow the stages in flight (the next two chunks'; the free buffer's count is
+    // these stores follow the stages in flight (the next chunks'; the free buffer's count is
     // reset when it is restaged)
     after += 0x1111;
     if (!more) break;
@@ -341,9 +512,69 @@ static int dkdv_grid(int nitems) {
   return nitems > ncu ? ncu : nitems;
 }
 
+// ---- which tile a launch takes
+// Cost of a head with KT-row items: 2 ceil(Lk / KT) dV / dK items of ceil(Lq / 32) chunks and
+// ceil(Lq / KT) dQ items of ceil(Lk / 32) chunks, a chunk priced at the item's KT rows.  The
+// bytes staged per chunk (32 KiB + 64 KT B) grow by 5 % from 128 to 160 rows, but the measured
+// time per chunk grows with the rows (x 1.24-1.29 for x 1.25: profiles/r09/dkdv_tiles.txt), so a
+// launch gains what the larger tile saves in padded rows and loses where it pads more
+// (L = 1024: 1120 rows against 1024, +9 % measured).
+static int64_t dkdv_cost(int Lq, int Lk, int KT) {
+  const auto cdiv = [](int x, int d) { return ((int64_t)x + d - 1) / d; };
+  return (2 * cdiv(Lk, KT) * cdiv(Lq, DK_QC) + cdiv(Lq, KT) * cdiv(Lk, DK_QC)) * KT;
+}
+
+// JMT_ATTN_DKDV_KT = 0 (the rule) / 128 / 160, read once; jmt_attn_dkdv_set_tile overrides it
+// in-process (tests and scripts/bench_dkdv.py compare the two tiles), -1 returns to the
+// environment's choice
+static int g_dkdv_tile = -1;
+static int dkdv_tile_pref() {
+  static const int env = [] {
+    const char* e = getenv("JMT_ATTN_DKDV_KT");
+    const int v = e ? atoi(e) : 0;
+    return v == 128 || v == 160 ? v : 0;
+  }();
+  return g_dkdv_tile < 0 ? env : g_dkdv_tile;
+}
+
+static int dkdv_plan(int Lq, int Lk, int64_t sdk_l, int64_t sdv_l, int64_t sdq_l, bool has_dq) {
+  constexpr int64_t KT = DkGeo<10>::KT;
+  // 160-row items read the tile-major hand-off only (dq != NULL) and need their 32-bit store
+  // offsets to cover 160 rows; where they do not, the launch is a valid 128-row one
+  if (!has_dq || Lq <= 0 || Lk <= 0 || KT * sdk_l * 2 >= (1LL << 31) ||
+      KT * sdv_l * 2 >= (1LL << 31) || KT * sdq_l * 2 >= (1LL << 31))
+    return 128;
+  const int pref = dkdv_tile_pref();
+  if (pref) return pref;
+  return dkdv_cost(Lq, Lk, 160) < dkdv_cost(Lq, Lk, 128) ? 160 : 128;   // ties keep 128
+}
+
+template <typename T, int NKG>
+static void dkdv_launch(const AttnDkdvArgs& a, int grid, hipStream_t st) {
+  constexpr int lds = DkGeo<NKG>::LDS;
+  static bool once = ((void)hipFuncSetAttribute((const void*)attn_dkdv_kernel<T, NKG>,
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds),
+                      true);
+  (void)once;
+  hipLaunchKernelGGL((attn_dkdv_kernel<T, NKG>), dim3(grid), dim3(512), (size_t)lds, st, a);
+}
+
 }  // namespace jmt
 
 using namespace jmt;
+
+extern "C" int jmt_attn_dkdv_set_tile(int kt) {
+  if (!(kt < 0 || kt == 0 || kt == 128 || kt == 160))
+    return set_error(JMT_ERR_ARG, "jmt_attn_dkdv_set_tile: %d is not 0, 128 or 160", kt);
+  g_dkdv_tile = kt < 0 ? -1 : kt;
+  return JMT_OK;
+}
+
+extern "C" int jmt_attn_dkdv_plan(int Lq, int Lk, int H, int64_t sdk_l, int64_t sdv_l,
+                                  int64_t sdq_l, int has_dq) {
+  (void)H;
+  return dkdv_plan(Lq, Lk, sdk_l, sdv_l, sdq_l, has_dq != 0);
+}
 
 extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const void* p,
                              const void* ds, int64_t ldp, const void* go, int64_t sgo_l,
@@ -351,6 +582,7 @@ extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const
                              const void* k, int64_t sk_l, int64_t sk_n, void* dk, int64_t sdk_l,
                              int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n, void* dq,
                              int64_t sdq_l, int64_t sdq_n, void* stream) {
+  constexpr int DK_KT = DkGeo<8>::KT;                  // the contract's tile: ldp, stride ranges
   if (N == 0 || Lk == 0) return JMT_OK;
   if (!((dt == JMT_BF16 || dt == JMT_F16) && dh == AT_DH))
     return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_dkdv: dtype %d / head dim %d not supported",
@@ -363,14 +595,13 @@ extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const
   const int64_t strides[] = {ldp, sgo_l, sgo_n, sq_l, sq_n, sdk_l, sdk_n, sdv_l, sdv_n};
   for (int i = 0; i < 9; ++i)
     JMT_CHECK_ARG(strides[i] % 8 == 0, "jmt_attn_dkdv: stride %d not a multiple of 8", i);
-  const int nkt = (Lk + DK_KT - 1) / DK_KT;
-  JMT_CHECK_ARG(ldp >= (int64_t)nkt * DK_KT,
-                "jmt_attn_dkdv: ldp must cover 128-key tiles (>= %d)", nkt * DK_KT);
+  JMT_CHECK_ARG(ldp >= (int64_t)((Lk + DK_KT - 1) / DK_KT) * DK_KT,
+                "jmt_attn_dkdv: ldp must cover 128-key tiles (>= %d)",
+                (Lk + DK_KT - 1) / DK_KT * DK_KT);
   JMT_CHECK_ARG(sdk_l >= H * AT_DH && sdv_l >= H * AT_DH &&
                     (int64_t)DK_KT * sdk_l * 2 < (1LL << 31) &&
                     (int64_t)DK_KT * sdv_l * 2 < (1LL << 31),
                 "jmt_attn_dkdv: dK / dV row stride out of range");
-  const int nqd = dq ? (Lq + DK_KT - 1) / DK_KT : 0;   // dQ items per (n, h)
   if (dq) {
     JMT_CHECK_ARG(k != nullptr && ((uintptr_t)k & 15) == 0 && ((uintptr_t)dq & 15) == 0 &&
                       sk_l % 8 == 0 && sk_n % 8 == 0 && sdq_l % 8 == 0 && sdq_n % 8 == 0,
@@ -378,7 +609,12 @@ extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const
     JMT_CHECK_ARG(sdq_l >= H * AT_DH && (int64_t)DK_KT * sdq_l * 2 < (1LL << 31) &&
                       (int64_t)Lk * sk_l * 2 < (1LL << 31),
                   "jmt_attn_dkdv: dQ / K row stride out of range");
+    // the tile-major region of head nh starts at nh Lq ldp: whole 32-key tiles only
+    JMT_CHECK_ARG(ldp % 32 == 0, "jmt_attn_dkdv: tile-major P / dS need ldp %% 32 == 0");
   }
+  const int kt = dkdv_plan(Lq, Lk, sdk_l, sdv_l, dq ? sdq_l : 0, dq != nullptr);
+  const int nkt = (Lk + kt - 1) / kt;
+  const int nqd = dq ? (Lq + kt - 1) / kt : 0;          // dQ items per (n, h)
   JMT_CHECK_ARG((int64_t)N * H * (2 * nkt + nqd) < (1LL << 31), "jmt_attn_dkdv: too many items");
   JMT_CHECK_ARG((int64_t)Lq * sgo_l * 2 < (1LL << 31) && (int64_t)Lq * sq_l * 2 < (1LL << 31) &&
                     (int64_t)Lq * ldp * 2 < (1LL << 31),
@@ -391,20 +627,14 @@ extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const
   a.sdq_l = sdq_l; a.sdq_n = sdq_n;
   a.Lq = Lq; a.Lk = Lk; a.H = H; a.nkt = nkt; a.nqd = nqd; a.ipn = 2 * nkt + nqd;
   a.nitems = N * H * a.ipn;
-  const dim3 grid(dkdv_grid(a.nitems));
+  const int grid = dkdv_grid(a.nitems);
   hipStream_t st = as_stream(stream);
-  if (dt == JMT_BF16) {
-    static bool once = ((void)hipFuncSetAttribute((const void*)attn_dkdv_kernel<__bf16>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, DK_LDS),
-                        true);
-    (void)once;
-    hipLaunchKernelGGL((attn_dkdv_kernel<__bf16>), grid, dim3(512), (size_t)DK_LDS, st, a);
+  if (kt == 160) {
+    if (dt == JMT_BF16) dkdv_launch<__bf16, 10>(a, grid, st);
+    else dkdv_launch<_Float16, 10>(a, grid, st);
   } else {
-    static bool once = ((void)hipFuncSetAttribute((const void*)attn_dkdv_kernel<_Float16>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, DK_LDS),
-                        true);
-    (void)once;
-    hipLaunchKernelGGL((attn_dkdv_kernel<_Float16>), grid, dim3(512), (size_t)DK_LDS, st, a);
+    if (dt == JMT_BF16) dkdv_launch<__bf16, 8>(a, grid, st);
+    else dkdv_launch<_Float16, 8>(a, grid, st);
   }
   JMT_LAUNCH_CHECK("jmt_attn_dkdv");
   return JMT_OK;

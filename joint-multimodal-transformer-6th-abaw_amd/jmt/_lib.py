@@ -105,6 +105,11 @@ _PROTOS = {
     "jmt_attn_dkdv": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp,
                               c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                               c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    # the tile (128 / 160 rows) jmt_attn_dkdv takes: (Lq, Lk, H, sdk_l, sdv_l, sdq_l, has_dq)
+    "jmt_attn_dkdv_plan": (c_int, [c_int, c_int, c_int, c_i64, c_i64, c_i64, c_int]),
+    # dev switch outside include/jmt.h: 128 / 160 force the tile where it is valid, 0 the rule,
+    # -1 returns to JMT_ATTN_DKDV_KT (csrc/attn_dkdv.hip)
+    "jmt_attn_dkdv_set_tile": (c_int, [c_int]),
     "jmt_noop": (c_int, [c_vp]),
     "jmt_small_attn_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
                                    c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,

@@ -1,5 +1,6 @@
 """jmt_attn_dkdv vs the two batched TN GEMMs it replaces (dK = dS^T Q, dV = P^T dO), same
-operands, interleaved in one process.   python scripts/bench_dkdv.py [--reps 30]"""
+operands, interleaved in one process.   python scripts/bench_dkdv.py [--reps 30]
+--tiles: the three-product launch (dq != NULL) with 128-row against 160-row items."""
 import argparse
 import json
 import os
@@ -29,12 +30,69 @@ def time_us(fn, reps):
     return ts[len(ts) // 2], ts[0]
 
 
+TILE_SHAPES = [(384, 300), (192, 300), (96, 1024)]          # --tiles: (N*H sequences, L)
+
+
+def tiles(reps, rounds):
+    """The three products (dq != NULL, tile-major P / dS) with 128-row against 160-row items
+    (jmt_attn_dkdv_set_tile), interleaved: median [min-max] us over rounds x reps launches, and the
+    tile the rule (jmt_attn_dkdv_plan) takes."""
+    from jmt import _lib
+    lib = _lib.load()
+    dev, E = "cuda", 512
+    for N, L in TILE_SHAPES:
+        g = torch.Generator(device=dev).manual_seed(1)
+        ldp = ops.attn_dkdv_ldp(L)
+        P = torch.rand(N, ldp // 32, L, 32, device=dev, generator=g).bfloat16()
+        dS = (torch.randn(N, ldp // 32, L, 32, device=dev, generator=g) * 0.1).bfloat16()
+        qkv = torch.randn(N, L, 3 * E, device=dev, generator=g).bfloat16().permute(1, 0, 2)
+        go = torch.randn(N, L, E, device=dev, generator=g).bfloat16().permute(1, 0, 2)
+        out = torch.empty(N, L, 3 * E, device=dev).bfloat16().permute(1, 0, 2)
+        st = lambda t: (t.stride(0), t.stride(1))
+
+        def run():
+            ops.attn_dkdv(BF16, N, 1, L, L, E, P, dS, ldp, go.data_ptr(), st(go),
+                          qkv.data_ptr(), st(qkv), out[..., E:].data_ptr(), st(out),
+                          out[..., 2 * E:].data_ptr(), st(out), qkv[..., E:].data_ptr(), st(qkv),
+                          out.data_ptr(), st(out))
+        ts = {128: [], 160: []}
+        try:
+            lib.jmt_attn_dkdv_set_tile(0)
+            rule = lib.jmt_attn_dkdv_plan(L, L, 1, out.stride(0), out.stride(0), out.stride(0), 1)
+            for _ in range(rounds):
+                for kt in (128, 160):
+                    lib.jmt_attn_dkdv_set_tile(kt)
+                    run()
+                    torch.cuda.synchronize()
+                    s = torch.cuda.Event(enable_timing=True)
+                    e = torch.cuda.Event(enable_timing=True)
+                    for _ in range(reps):
+                        s.record()
+                        run()
+                        e.record()
+                        e.synchronize()
+                        ts[kt].append(s.elapsed_time(e) * 1e3)
+        finally:
+            lib.jmt_attn_dkdv_set_tile(-1)
+        line = {"shape": f"N*H={N} L={L}", "rule": rule}
+        for kt, v in ts.items():
+            v.sort()
+            line[str(kt)] = {"med_us": round(v[len(v) // 2], 1), "min_us": round(v[0], 1),
+                             "max_us": round(v[-1], 1)}
+        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--shapes", type=int, nargs="*", help="indices into SHAPES")
     ap.add_argument("--only", choices=["dkdv", "gemm"], help="time one implementation")
+    ap.add_argument("--tiles", action="store_true",
+                    help="128-row against 160-row items of the three-product launch")
+    ap.add_argument("--rounds", type=int, default=4, help="--tiles: interleaved rounds")
     args = ap.parse_args()
+    if args.tiles:
+        return tiles(args.reps, args.rounds)
     dev = "cuda"
     E = 512
     for i, (N, L) in enumerate(SHAPES):
