@@ -255,6 +255,39 @@ int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const void* p, c
                   int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n, void* dq,
                   int64_t sdq_l, int64_t sdq_n, void* stream);
 
+/* Shared queries (round 10; added to ABI 7, nothing else changes): the N sequences are npair =
+ * N / spp pairs (at most 8) of spp sequences each, and sequence n = p*spp + b reads the Q rows of
+ * sequence qtab[p]*spp + b of the q buffer (qtab[p] <= p, and qtab[qtab[p]] == qtab[p]: a source
+ * is a first use).  Only Q's batch index changes: K, V, O, dO, lse, P and dS stay per sequence.
+ * With the identity table the results are bitwise those of the unshared entry points, and with
+ * any table bitwise those of the unshared entry points on a Q buffer that holds each query once
+ * per sequence.
+ *   jmt_attn_fwd_sq: as jmt_attn_fwd on the whole-row kernel (Lq > 64, Lk K / V rows below 2 GiB).
+ *   jmt_attn_bwd_sq: as jmt_attn_bwd with dq == NULL (tile-major P and dS only).
+ *   jmt_attn_dkdv_sq: as jmt_attn_dkdv with dq != NULL.  merge_dq == 0: dK reads the shared Q and
+ *     dQ is written per sequence.  merge_dq != 0: ONE dQ per shared query, dQ = dS_i K_i + dS_j K_j
+ *     over the two sequences i < j that use it, summed in fp32 and rounded once, written to the
+ *     first use's rows of dq; the second use's rows of dq are not written.  Every query must then
+ *     be used exactly twice.  Both tiles contract in the same order (bitwise equal).
+ * Anything else (fp32, dh != 512, Lq <= 64 in the forward, dq == NULL in jmt_attn_dkdv_sq, a
+ * table merge_dq cannot take) returns JMT_ERR_UNSUPPORTED before anything is launched. */
+int jmt_attn_fwd_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* q, int64_t sq_l,
+                    int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                    int64_t sv_l, int64_t sv_n, void* o, int64_t so_l, int64_t so_n, float scale,
+                    float* lse, int spp, const int* qtab, int npair, void* stream);
+int jmt_attn_bwd_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* go, int64_t sgo_l,
+                    int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n, const void* q,
+                    int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                    const void* v, int64_t sv_l, int64_t sv_n, const float* lse, void* p_out,
+                    void* ds_out, int64_t ldp, float scale, int spp, const int* qtab, int npair,
+                    void* stream);
+int jmt_attn_dkdv_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* p, const void* ds,
+                     int64_t ldp, const void* go, int64_t sgo_l, int64_t sgo_n, const void* q,
+                     int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                     void* dk, int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l,
+                     int64_t sdv_n, void* dq, int64_t sdq_l, int64_t sdq_n, int spp,
+                     const int* qtab, int npair, int merge_dq, void* stream);
+
 /* Fused attention over short sequences, the whole backward in one kernel (Lq, Lk <= 32, 16-bit,
  * dh = 512; the batch-axis self-attention of mm_transformers.py:119-146 at B = 32 and every
  * attention of the T = 16 real-data configuration): same element addressing as jmt_attn_*,

@@ -177,6 +177,60 @@ int main() {
                                               algn, 512, 512, algn, 512, 512, algn, 512, 512,
                                               algn, 512, 512, fnull, algn, algn, 300, nullptr,
                                               0, 0, 0.1f, nullptr));
+  // shared queries: the table is checked before anything else of the launch
+  {
+    const int id2[2] = {0, 1}, fwd[2] = {1, 1}, chain[3] = {0, 0, 1}, three[3] = {0, 0, 0};
+    const int big[9] = {0, 1, 2, 3, 4, 5, 6, 7, 8};
+    expect_err("attn_fwd_sq fp32", jmt_attn_fwd_sq(JMT_F32, 2, 1, 300, 300, 512, algn, 512, 512,
+                                                   algn, 512, 512, algn, 512, 512, algn, 512, 512,
+                                                   0.1f, fnull, 1, id2, 2, nullptr));
+    expect_err("attn_fwd_sq Lq 64", jmt_attn_fwd_sq(JMT_BF16, 2, 1, 64, 300, 512, algn, 512, 512,
+                                                    algn, 512, 512, algn, 512, 512, algn, 512,
+                                                    512, 0.1f, fnull, 1, id2, 2, nullptr));
+    expect_err("attn_fwd_sq null table", jmt_attn_fwd_sq(JMT_BF16, 2, 1, 300, 300, 512, algn, 512,
+                                                         512, algn, 512, 512, algn, 512, 512,
+                                                         algn, 512, 512, 0.1f, fnull, 1, nullptr,
+                                                         2, nullptr));
+    expect_err("attn_fwd_sq N != npair spp", jmt_attn_fwd_sq(JMT_BF16, 3, 1, 300, 300, 512, algn,
+                                                             512, 512, algn, 512, 512, algn, 512,
+                                                             512, algn, 512, 512, 0.1f, fnull, 1,
+                                                             id2, 2, nullptr));
+    expect_err("attn_fwd_sq 9 pairs", jmt_attn_fwd_sq(JMT_BF16, 9, 1, 300, 300, 512, algn, 512,
+                                                      512, algn, 512, 512, algn, 512, 512, algn,
+                                                      512, 512, 0.1f, fnull, 1, big, 9, nullptr));
+    expect_err("attn_fwd_sq forward source", jmt_attn_fwd_sq(JMT_BF16, 2, 1, 300, 300, 512, algn,
+                                                             512, 512, algn, 512, 512, algn, 512,
+                                                             512, algn, 512, 512, 0.1f, fnull, 1,
+                                                             fwd, 2, nullptr));
+    expect_err("attn_bwd_sq chained source", jmt_attn_bwd_sq(JMT_BF16, 3, 1, 300, 300, 512, algn,
+                                                             512, 512, algn, 512, 512, algn, 512,
+                                                             512, algn, 512, 512, algn, 512, 512,
+                                                             fnull, algn, algn, 384, 0.1f, 1,
+                                                             chain, 3, nullptr));
+    expect_err("attn_bwd_sq ldp", jmt_attn_bwd_sq(JMT_BF16, 2, 1, 300, 300, 512, algn, 512, 512,
+                                                  algn, 512, 512, algn, 512, 512, algn, 512, 512,
+                                                  algn, 512, 512, fnull, algn, algn, 300, 0.1f, 1,
+                                                  id2, 2, nullptr));
+    expect_err("attn_dkdv_sq dq null", jmt_attn_dkdv_sq(JMT_BF16, 2, 1, 300, 300, 512, algn, algn,
+                                                        384, algn, 512, 512, algn, 512, 512, algn,
+                                                        512, 512, algn, 512, 512, algn, 512, 512,
+                                                        nullptr, 0, 0, 1, id2, 2, 0, nullptr));
+    expect_err("attn_dkdv_sq spp 0", jmt_attn_dkdv_sq(JMT_BF16, 2, 1, 300, 300, 512, algn, algn,
+                                                      384, algn, 512, 512, algn, 512, 512, algn,
+                                                      512, 512, algn, 512, 512, algn, 512, 512,
+                                                      algn, 512, 512, 0, id2, 2, 0, nullptr));
+    // merged dQ: a query used three times, and one used once
+    expect_err("attn_dkdv_sq merge 3 uses", jmt_attn_dkdv_sq(JMT_BF16, 3, 1, 300, 300, 512, algn,
+                                                             algn, 384, algn, 512, 512, algn, 512,
+                                                             512, algn, 512, 512, algn, 512, 512,
+                                                             algn, 512, 512, algn, 512, 512, 1,
+                                                             three, 3, 1, nullptr));
+    expect_err("attn_dkdv_sq merge 1 use", jmt_attn_dkdv_sq(JMT_BF16, 2, 1, 300, 300, 512, algn,
+                                                            algn, 384, algn, 512, 512, algn, 512,
+                                                            512, algn, 512, 512, algn, 512, 512,
+                                                            algn, 512, 512, algn, 512, 512, 1, id2,
+                                                            2, 1, nullptr));
+  }
   expect_err("small_attn_fwd null", jmt_small_attn_fwd(JMT_BF16, 4, 1, 6, 6, 512, nullptr, 512,
                                                        512, nullptr, 512, 512, nullptr, 512, 512,
                                                        nullptr, 512, 512, 0.1f, fnull, nullptr));

@@ -67,6 +67,7 @@ struct AttnFwdArgs {
   int Lq, Lk, H, nitems;
   float scale_log2;
   uint64_t* stamps;
+  QShare qs;                        // the whole-row kernel only (jmt_attn_fwd_sq)
 };
 
 // Phase stamps (diagnostic build only, STAMP = true): s_memtime at each phase boundary of every
@@ -621,7 +622,7 @@ constexpr int AP_LDS = 4 * AP_KT * AT_ROWB;
 // (s_memtime of block gridDim / 2, waves 0 and 4, into p.dq as a uint64 buffer of
 // 2 x 256 x 64: phases 8 t + {0 tile start, 1 DMA issued, 2 MFMAs issued, 3 softmax + stores
 // issued, 4 end wait, 5 barrier} of the block's first 31 tiles, 255 / 254 item start / end)
-template <typename T, int DBG = 0>
+template <typename T, int DBG = 0, bool SQ = false>
 __global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(AttnBwdArgs p) {
   int tcount = 0;
   auto st = [&](int phase) {
@@ -652,7 +653,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(AttnBwdArgs p) {
   F qf[16], df[16], of[16];
   auto load_qd = [&](int n_, int hd_, int q0_) {
     const int64_t qc_ = min(q0_ + 16 * w + li, p.Lq - 1), coff = (int64_t)hd_ * AT_DH + 8 * g;
-    const T* qrow = (const T*)p.q + (int64_t)n_ * p.sq_n + qc_ * p.sq_l + coff;
+    const T* qrow = (const T*)p.q + (int64_t)q_seq<SQ>(p.qs, n_) * p.sq_n + qc_ * p.sq_l + coff;
     const T* drow = (const T*)p.go + (int64_t)n_ * p.sgo_n + qc_ * p.sgo_l + coff;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
@@ -887,7 +888,7 @@ constexpr int AR_VB = 4;             // V fragments per P V read batch
 // DBG (ablations, timing only, wrong results; JMT_ATTN_FWD_ROWS_DBG in the diagnostic build):
 // 2 no score reads / MFMAs, 4 no softmax, 8 no K / V DMA after an item's tile 0, 16 no P V reads /
 // MFMAs, 32 no O / lse stores.
-template <typename T, int DBG = 0>
+template <typename T, int DBG = 0, bool SQ = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
   typedef typename Frag16<T>::t F;
   typedef typename Frag16<T>::h Hf;
@@ -909,7 +910,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
   // lane (li, g): row q0 + 16 w + li, dims 32 ks + 8 g .. +7 of fragment ks
   F qf[16];
   auto load_q = [&](int n_, int hd_, int q0_) {
-    const T* qrow = (const T*)p.q + (int64_t)n_ * p.sq_n + hd_ * AT_DH +
+    const T* qrow = (const T*)p.q + (int64_t)q_seq<SQ>(p.qs, n_) * p.sq_n + hd_ * AT_DH +
                     (int64_t)min(q0_ + 16 * w + li, p.Lq - 1) * p.sq_l + 8 * g;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) qf[ks] = *(const F*)(qrow + 32 * ks);
@@ -1220,10 +1221,12 @@ extern "C" int jmt_attn_supported(int dt, int dh) {
   return (dt == JMT_BF16 || dt == JMT_F16) && dh == AT_DH;
 }
 
-extern "C" int jmt_attn_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
-                            int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
-                            const void* v, int64_t sv_l, int64_t sv_n, void* o, int64_t so_l,
-                            int64_t so_n, float scale, float* lse, void* stream) {
+// jmt_attn_fwd (qs == NULL) and jmt_attn_fwd_sq (qs: the packed query table; the whole-row
+// kernel only)
+static int attn_fwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                         int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                         const void* v, int64_t sv_l, int64_t sv_n, void* o, int64_t so_l,
+                         int64_t so_n, float scale, float* lse, const QShare* qs, void* stream) {
   if (N == 0 || Lq == 0) return JMT_OK;
   if (!jmt_attn_supported(dt, dh))
     return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_fwd: dtype %d / head dim %d not supported",
@@ -1235,10 +1238,15 @@ extern "C" int jmt_attn_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
   // bit (include/jmt.h).
   const bool rows = fwd_rows_on() && Lq > AT_QT && (int64_t)Lk * sk_l * 2 < (1LL << 31) &&
                     (int64_t)Lk * sv_l * 2 < (1LL << 31);
+  if (qs && !rows)
+    return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_fwd_sq: the whole-row kernel only (Lq > %d, "
+                                          "Lk K / V rows below 2 GiB, JMT_ATTN_FWD_ROWS on)",
+                     AT_QT);
   const int qt = rows ? AR_QT : AT_QT;
   int rc = check_common("jmt_attn_fwd", N, H, Lq, Lk, qt, ptrs, 4, strides, 8);
   if (rc != JMT_OK) return rc;
   AttnFwdArgs a = {};
+  if (qs) a.qs = *qs;
   a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
   a.sq_l = sq_l; a.sq_n = sq_n; a.sk_l = sk_l; a.sk_n = sk_n; a.sv_l = sv_l; a.sv_n = sv_n;
   a.so_l = so_l; a.so_n = so_n;
@@ -1269,6 +1277,21 @@ extern "C" int jmt_attn_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
       return JMT_OK;
     }
 #endif
+    if (qs) {
+      if (dt == JMT_BF16) {
+        static bool once = (set_lds(attn_fwd_rows_kernel<__bf16, 0, true>, AR_LDS), true);
+        (void)once;
+        hipLaunchKernelGGL((attn_fwd_rows_kernel<__bf16, 0, true>), grid, dim3(512),
+                           (size_t)AR_LDS, st, a);
+      } else {
+        static bool once = (set_lds(attn_fwd_rows_kernel<_Float16, 0, true>, AR_LDS), true);
+        (void)once;
+        hipLaunchKernelGGL((attn_fwd_rows_kernel<_Float16, 0, true>), grid, dim3(512),
+                           (size_t)AR_LDS, st, a);
+      }
+      JMT_LAUNCH_CHECK("jmt_attn_fwd_sq");
+      return JMT_OK;
+    }
     if (dt == JMT_BF16) {
       static bool once = (set_lds(attn_fwd_rows_kernel<__bf16>, AR_LDS), true);
       (void)once;
@@ -1305,13 +1328,38 @@ extern "C" int jmt_attn_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
   return JMT_OK;
 }
 
-extern "C" int jmt_attn_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
-                            int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
-                            int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
-                            const void* k, int64_t sk_l, int64_t sk_n, const void* v,
-                            int64_t sv_l, int64_t sv_n, const float* lse, void* p_out,
-                            void* ds_out, int64_t ldp, void* dq, int64_t sdq_l, int64_t sdq_n,
-                            float scale, void* stream) {
+extern "C" int jmt_attn_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                            int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                            const void* v, int64_t sv_l, int64_t sv_n, void* o, int64_t so_l,
+                            int64_t so_n, float scale, float* lse, void* stream) {
+  return attn_fwd_impl(dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o, so_l,
+                       so_n, scale, lse, nullptr, stream);
+}
+
+extern "C" int jmt_attn_fwd_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                               int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                               int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n, void* o,
+                               int64_t so_l, int64_t so_n, float scale, float* lse, int spp,
+                               const int* qtab, int npair, void* stream) {
+  if (N == 0 || Lq == 0) return JMT_OK;
+  if (!jmt_attn_supported(dt, dh))
+    return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_fwd_sq: dtype %d / head dim %d not supported",
+                     dt, dh);
+  QShare qs = {};
+  int rc = qshare_pack("jmt_attn_fwd_sq", N, spp, qtab, npair, &qs);
+  if (rc != JMT_OK) return rc;
+  return attn_fwd_impl(dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o, so_l,
+                       so_n, scale, lse, &qs, stream);
+}
+
+// jmt_attn_bwd (qs == NULL) and jmt_attn_bwd_sq (qs: the packed query table; dq == NULL only)
+static int attn_bwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                         int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n,
+                         const void* q, int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                         int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n,
+                         const float* lse, void* p_out, void* ds_out, int64_t ldp, void* dq,
+                         int64_t sdq_l, int64_t sdq_n, float scale, const QShare* qs,
+                         void* stream) {
   if (N == 0 || Lq == 0) return JMT_OK;
   if (!jmt_attn_supported(dt, dh))
     return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_bwd: dtype %d / head dim %d not supported",
@@ -1331,6 +1379,7 @@ extern "C" int jmt_attn_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
                   "jmt_attn_bwd (dq = NULL): ldp must be a multiple of 32 covering Lk, Lq rows "
                   "of ldp 16-bit values below 1 GiB and Lk K / V rows below 2 GiB");
     AttnBwdArgs a = {};
+    if (qs) a.qs = *qs;
     a.go = go; a.o = o; a.q = q; a.k = k; a.v = v; a.lse = lse;
     a.pbuf = p_out; a.dsbuf = ds_out; a.dq = nullptr;
     a.sgo_l = sgo_l; a.sgo_n = sgo_n; a.so_l = so_l; a.so_n = so_n; a.sq_l = sq_l; a.sq_n = sq_n;
@@ -1364,6 +1413,21 @@ extern "C" int jmt_attn_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
       return JMT_OK;
     }
 #endif
+    if (qs) {
+      if (dt == JMT_BF16) {
+        static bool once = (set_lds(attn_bwd_pds_kernel<__bf16, 0, true>, AP_LDS), true);
+        (void)once;
+        hipLaunchKernelGGL((attn_bwd_pds_kernel<__bf16, 0, true>), grid, dim3(512),
+                           (size_t)AP_LDS, st, a);
+      } else {
+        static bool once = (set_lds(attn_bwd_pds_kernel<_Float16, 0, true>, AP_LDS), true);
+        (void)once;
+        hipLaunchKernelGGL((attn_bwd_pds_kernel<_Float16, 0, true>), grid, dim3(512),
+                           (size_t)AP_LDS, st, a);
+      }
+      JMT_LAUNCH_CHECK("jmt_attn_bwd_sq");
+      return JMT_OK;
+    }
     if (dt == JMT_BF16) {
       static bool once = (set_lds(attn_bwd_pds_kernel<__bf16>, AP_LDS), true);
       (void)once;
@@ -1401,3 +1465,33 @@ extern "C" int jmt_attn_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
   return JMT_OK;
 }
 
+extern "C" int jmt_attn_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                            int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
+                            int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
+                            const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                            int64_t sv_l, int64_t sv_n, const float* lse, void* p_out,
+                            void* ds_out, int64_t ldp, void* dq, int64_t sdq_l, int64_t sdq_n,
+                            float scale, void* stream) {
+  return attn_bwd_impl(dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
+                       sk_l, sk_n, v, sv_l, sv_n, lse, p_out, ds_out, ldp, dq, sdq_l, sdq_n, scale,
+                       nullptr, stream);
+}
+
+extern "C" int jmt_attn_bwd_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                               int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
+                               int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
+                               const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                               int64_t sv_l, int64_t sv_n, const float* lse, void* p_out,
+                               void* ds_out, int64_t ldp, float scale, int spp, const int* qtab,
+                               int npair, void* stream) {
+  if (N == 0 || Lq == 0) return JMT_OK;
+  if (!jmt_attn_supported(dt, dh))
+    return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_bwd_sq: dtype %d / head dim %d not supported",
+                     dt, dh);
+  QShare qs = {};
+  int rc = qshare_pack("jmt_attn_bwd_sq", N, spp, qtab, npair, &qs);
+  if (rc != JMT_OK) return rc;
+  return attn_bwd_impl(dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
+                       sk_l, sk_n, v, sv_l, sv_n, lse, p_out, ds_out, ldp, nullptr, 0, 0, scale,
+                       &qs, stream);
+}

@@ -9,6 +9,43 @@ namespace jmt {
 constexpr int AT_DH = 512;          // head dim of the fused kernels
 constexpr int AT_ROWB = 1024;       // bytes per image row (DH 16-bit values)
 
+// Query sharing (the *_sq entry points): the N sequences of a launch are npair = N / spp pairs of
+// spp sequences each, and sequence n = p spp + b reads the Q rows of sequence tab[p] spp + b.
+// K, V, O, dO, lse, P and dS stay per sequence; only Q's batch index changes.  tab holds the
+// pairs' sources as 4-bit fields (at most 8 pairs).
+// n is wave-uniform wherever it is decoded from an item, and so is the source.
+struct QShare {
+  int spp;
+  uint32_t tab;
+};
+// The kernels are compiled twice: SQ = false (the unshared entry points: the parent's code, no
+// table in sight) and SQ = true.
+template <bool SQ>
+__device__ __forceinline__ int q_seq(const QShare& s, int n) {
+  if constexpr (!SQ) return n;
+  const int p = n / s.spp;
+  return (int)((s.tab >> (4 * p)) & 15u) * s.spp + (n - p * s.spp);
+}
+
+// Host side: check a per-pair source table and pack it.  A source is a first use (tab[p] <= p,
+// tab[tab[p]] == tab[p]), so every sequence a kernel reads Q from lies inside the N the caller
+// passed and the unshared range checks of the strides cover the shared addresses too.
+static inline int qshare_pack(const char* name, int N, int spp, const int* tab, int npair,
+                              QShare* out) {
+  JMT_CHECK_ARG(tab != nullptr && spp > 0 && npair >= 1 && npair <= 8 &&
+                    (int64_t)spp * npair == N,
+                "%s: query table needs 1-8 pairs of spp sequences with npair * spp == N", name);
+  uint32_t bits = 0;
+  for (int p = 0; p < npair; ++p) {
+    JMT_CHECK_ARG(tab[p] >= 0 && tab[p] <= p && tab[tab[p]] == tab[p],
+                  "%s: query table entry %d (%d) is not an earlier first use", name, p, tab[p]);
+    bits |= (uint32_t)tab[p] << (4 * p);
+  }
+  out->spp = spp;
+  out->tab = bits;
+  return JMT_OK;
+}
+
 // arguments of the long-sequence attention backward (attn.hip attn_bwd_kernel)
 struct AttnBwdArgs {
   const void* go;
@@ -23,6 +60,7 @@ struct AttnBwdArgs {
   int64_t sgo_l, sgo_n, so_l, so_n, sq_l, sq_n, sk_l, sk_n, sv_l, sv_n, sdq_l, sdq_n, ldp;
   int Lq, Lk, H, nitems;
   float scale, scale_log2;
+  QShare qs;                        // the P / dS kernel only (jmt_attn_bwd_sq)
 };
 
 // byte offset of logical byte b of row `row` in a swizzled image

@@ -44,6 +44,12 @@
 //  Each output element is contracted over the same 32-deep chunks in the same order by both, so
 //  the results are bitwise equal.
 //
+// Shared queries (template flag SQ, jmt_attn_dkdv_sq): the dK role reads Q through the per-pair
+// table of attn_common.h (QShare); with `mrg` the two uses of a query share ONE dQ item whose
+// chunk loop runs over the first use's keys and then the second's (dk_decode).  The seam is a
+// change of source pointers inside the DMA stream; NDMA per stage and NST per item are unchanged,
+// so the accounting below holds as it stands.  SQ = false is the code of before.
+//
 // vmcnt accounting.  Every wait in the chunk loop is s_waitcnt vmcnt(S NDMA + B NST) with
 // immediate operands: S later stages and B items' output stores stay in flight behind the
 // awaited stage.  This is exact only if EVERY wave issues the same NDMA DMA wave-instructions per
@@ -100,6 +106,12 @@ struct AttnDkdvArgs {
   void* dq;
   int64_t ldp, sgo_l, sgo_n, sq_l, sq_n, sk_l, sk_n, sdk_l, sdk_n, sdv_l, sdv_n, sdq_l, sdq_n;
   int Lq, Lk, H, nkt, nqd, ipn, nitems;
+  // jmt_attn_dkdv_sq: the dK role reads the Q of sequence q_seq(qs, n).  With mrg (one dQ per
+  // shared query) the items are laid out per group = (first use n1, second use n2, head):
+  // n1 = mg_first[u] spp + b, n2 = mg_second[u] spp + b for group (u spp + b) H + h (4-bit fields)
+  QShare qs;
+  int mrg;
+  uint32_t mg_first, mg_second;
 };
 
 // byte offset of 16-B chunk `c` of row `r` of the P / dS image of a 128-key item (256-B rows)
@@ -126,12 +138,45 @@ __device__ __forceinline__ int qimg_off(int r, int c) {
 // item -> (n H + h, n, h, product (0: dV, 1: dK, 2: dQ), first key (0, 1) or query (2), chunks).
 // Per (n, h): nkt dV items, nkt dK items (KT-key tiles, the contraction over queries in 32-row
 // chunks), then nqd dQ items (KT-query tiles, the contraction over keys in 32-key chunks).
+// Merged dQ (a.mrg): per group the nqd dQ items first (the long ones: they contract over the
+// keys of BOTH sequences, nch = 2 nch1, chunks [0, nch1) from n / nh and [nch1, nch) from n2 / nh2,
+// each half masked at its own Lk), then the first use's 2 nkt dV / dK items, then the second
+// use's.  A group's items are contiguous, so an XCD's range keeps the items that read one head's
+// dS together as before, and the long items are spread over the walk, one group apart.
 struct DkItem {
-  int nh, n, hd, role, k0, nch;
+  int nh, n, hd, role, k0, nch, nch1, n2, nh2;
 };
-template <int KT>
+template <int KT, bool SQ>
 __device__ __forceinline__ DkItem dk_decode(const AttnDkdvArgs& a, int it) {
   DkItem d;
+  if (SQ && a.mrg) {
+    const int gi = it / a.ipn;
+    int r = it - gi * a.ipn;
+    const int sb = gi / a.H;                            // u spp + b
+    d.hd = gi - sb * a.H;
+    const int u = sb / a.qs.spp, b = sb - u * a.qs.spp;
+    const int n1 = (int)((a.mg_first >> (4 * u)) & 15u) * a.qs.spp + b;
+    const int n2 = (int)((a.mg_second >> (4 * u)) & 15u) * a.qs.spp + b;
+    if (r < a.nqd) {
+      d.role = 2;
+      d.k0 = r * KT;
+      d.nch1 = (a.Lk + DK_QC - 1) / DK_QC;
+      d.nch = 2 * d.nch1;
+      d.n = n1;
+      d.n2 = n2;
+    } else {
+      r -= a.nqd;
+      const int second = r >= 2 * a.nkt;
+      r -= second * 2 * a.nkt;
+      d.role = r >= a.nkt;
+      d.k0 = (r - d.role * a.nkt) * KT;
+      d.nch = d.nch1 = (a.Lq + DK_QC - 1) / DK_QC;
+      d.n = d.n2 = second ? n2 : n1;
+    }
+    d.nh = d.n * a.H + d.hd;
+    d.nh2 = d.n2 * a.H + d.hd;
+    return d;
+  }
   d.nh = it / a.ipn;
   const int r = it - d.nh * a.ipn;
   if (r < 2 * a.nkt) {
@@ -145,6 +190,9 @@ __device__ __forceinline__ DkItem dk_decode(const AttnDkdvArgs& a, int it) {
   }
   d.n = d.nh / a.H;
   d.hd = d.nh - d.n * a.H;
+  d.nch1 = d.nch;
+  d.n2 = d.n;
+  d.nh2 = d.nh;
   return d;
 }
 
@@ -152,15 +200,20 @@ __device__ __forceinline__ DkItem dk_decode(const AttnDkdvArgs& a, int it) {
 // tile (keys k0 .. k0+127): 4 + 1 DMA wave-instructions per wave.  Row offsets in 32-bit byte
 // arithmetic from a per-head base (the host checks Lq rows fit): the 64-bit row products of
 // stage_rows cost ~25 scalar instructions per DMA, and the CU's one scalar unit serves all 8 waves.
-template <typename T>
+// `c` is the item's chunk: contraction rows 32 c .. +31, or for the second half of a merged dQ
+// item (c >= nch1) keys 32 (c - nch1) .. +31 of the second use's sequence.
+template <typename T, bool SQ>
 __device__ __forceinline__ void dkdv_stage(char* st, const AttnDkdvArgs& a, const DkItem& d,
-                                           int q0) {
+                                           int c) {
   const int lane = threadIdx.x & 63;
   const int wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool second = SQ && c >= d.nch1;                // merged dQ items only
+  const int q0 = DK_QC * (second ? c - d.nch1 : c);
   if (d.role == 2) {
+    const int sn = second ? d.n2 : d.n, snh = second ? d.nh2 : d.nh;
     // dQ chunk: K rows q0 .. q0+31 (here q0 is the first KEY of the chunk) and the dS tile of the
     // item's 128 queries x those 32 keys (one wave-instruction per wave: 16 rows of 64 B)
-    const char* kb = (const char*)((const T*)a.k + (int64_t)d.n * a.sk_n + d.hd * AT_DH);
+    const char* kb = (const char*)((const T*)a.k + (int64_t)sn * a.sk_n + d.hd * AT_DH);
     const int ldk = (int)(a.sk_l * (int64_t)sizeof(T));
 #pragma unroll
     for (int i = 0; i < DK_QC / 8; ++i) {
@@ -170,12 +223,12 @@ __device__ __forceinline__ void dkdv_stage(char* st, const AttnDkdvArgs& a, cons
       glds16_asm(kb + (unsigned)(src * ldk) + off, st + r * AT_ROWB);
     }
     const int r = 16 * wu + (lane >> 2);                // dS image row (query d.k0 + r)
-    const int c = (lane & 3) ^ ((r >> 2) & 3);          // the logical chunk this lane's 16 B hold
+    const int lc = (lane & 3) ^ ((r >> 2) & 3);         // the logical chunk this lane's 16 B hold
     const int src_row = min(d.k0 + r, a.Lq - 1);
-    JMT_DCHECK(src_row >= 0 && q0 + 8 * c + 8 <= a.ldp);
+    JMT_DCHECK(src_row >= 0 && q0 + 8 * lc + 8 <= a.ldp);
     // tile-major dS (jmt_attn_bwd with dq = NULL): [key tile q0 / 32][query][32 keys]
-    const char* pb = (const char*)((const T*)a.ds + (int64_t)d.nh * a.Lq * a.ldp);
-    glds16_asm(pb + (unsigned)(((q0 >> 5) * a.Lq + src_row) * 64) + 16 * c,
+    const char* pb = (const char*)((const T*)a.ds + (int64_t)snh * a.Lq * a.ldp);
+    glds16_asm(pb + (unsigned)(((q0 >> 5) * a.Lq + src_row) * 64) + 16 * lc,
                st + DK_IMG + wu * 1024);
     return;
   }
@@ -185,7 +238,7 @@ __device__ __forceinline__ void dkdv_stage(char* st, const AttnDkdvArgs& a, cons
     rb = (const char*)((const T*)a.go + (int64_t)d.n * a.sgo_n + d.hd * AT_DH);
     ldb = (int)(a.sgo_l * (int64_t)sizeof(T));
   } else {
-    rb = (const char*)((const T*)a.q + (int64_t)d.n * a.sq_n + d.hd * AT_DH);
+    rb = (const char*)((const T*)a.q + (int64_t)q_seq<SQ>(a.qs, d.n) * a.sq_n + d.hd * AT_DH);
     ldb = (int)(a.sq_l * (int64_t)sizeof(T));
   }
 #pragma unroll
@@ -220,12 +273,15 @@ __device__ __forceinline__ void dkdv_stage(char* st, const AttnDkdvArgs& a, cons
 // the head's region (ldp / 32 - 1: ldp covers 128-key tiles only, and the tile after belongs to
 // the next head; a clamped tile feeds keys past Lk, which are not stored).  dQ: 160 queries x the
 // chunk's 32 keys (qimg_off), from hand-off tile q0 / 32.
-template <typename T>
+template <typename T, bool SQ>
 __device__ __forceinline__ void dkdv_stage160(uint32_t st, const AttnDkdvArgs& a, const DkItem& d,
-                                              int q0) {
+                                              int ch) {
   typedef DkGeo<10> G;
   const int lane = threadIdx.x & 63;
   const int wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool second = SQ && ch >= d.nch1;               // merged dQ items only (as dkdv_stage)
+  const int q0 = DK_QC * (second ? ch - d.nch1 : ch);
+  const int snh = second ? d.nh2 : d.nh;
   const char* rb;
   int ldb, clen;
   if (d.role == 0) {
@@ -233,11 +289,11 @@ __device__ __forceinline__ void dkdv_stage160(uint32_t st, const AttnDkdvArgs& a
     ldb = (int)(a.sgo_l * (int64_t)sizeof(T));
     clen = a.Lq;
   } else if (d.role == 1) {
-    rb = (const char*)((const T*)a.q + (int64_t)d.n * a.sq_n + d.hd * AT_DH);
+    rb = (const char*)((const T*)a.q + (int64_t)q_seq<SQ>(a.qs, d.n) * a.sq_n + d.hd * AT_DH);
     ldb = (int)(a.sq_l * (int64_t)sizeof(T));
     clen = a.Lq;
   } else {
-    rb = (const char*)((const T*)a.k + (int64_t)d.n * a.sk_n + d.hd * AT_DH);
+    rb = (const char*)((const T*)a.k + (int64_t)(second ? d.n2 : d.n) * a.sk_n + d.hd * AT_DH);
     ldb = (int)(a.sk_l * (int64_t)sizeof(T));
     clen = a.Lk;
   }
@@ -250,7 +306,7 @@ __device__ __forceinline__ void dkdv_stage160(uint32_t st, const AttnDkdvArgs& a
     glds16_sv(rb + (unsigned)(src * ldb), off, st + r * AT_ROWB);
   }
   const char* pb = (const char*)((const T*)(d.role == 0 ? a.p : a.ds) +
-                                 (int64_t)d.nh * a.Lq * a.ldp);
+                                 (int64_t)snh * a.Lq * a.ldp);
   const int ntile = (int)(a.ldp >> 5);                  // 32-key tiles of the head's region
   if (lane < G::PLANES) {
 #pragma unroll
@@ -305,7 +361,7 @@ __device__ __forceinline__ void dkdv_wait(int stages, int stores) {
 // with the paired reads, 0 without, and 40 % fewer active LDS cycles (profiles/r09/dkdv_pmc*.txt).
 #define DK_NO_MERGE() asm volatile("" ::: "memory")
 
-template <typename T, int NKG>
+template <typename T, int NKG, bool SQ>
 __global__ __launch_bounds__(512, 2) void attn_dkdv_kernel(AttnDkdvArgs a) {
   typedef typename Frag16<T>::t F;
   typedef typename Frag16<T>::h Hf;
@@ -352,22 +408,22 @@ __global__ __launch_bounds__(512, 2) void attn_dkdv_kernel(AttnDkdvArgs a) {
 
   // issue cursor: the chunk whose stage goes out next (runs NS - 1 chunks ahead of the compute)
   int is_item = item, is_c = 0;
-  DkItem is_d = dk_decode<KT>(a, item);
+  DkItem is_d = dk_decode<KT, SQ>(a, item);
   bool is_ok = true;
   int is_buf = 0;
   unsigned after = 0;      // 4 bits per buffer: store batches issued after the stage it holds
   int inflight = 0;        // stages issued and not yet waited for
   auto issue = [&]() {
     if (is_ok) {
-      if constexpr (NKG == 8) dkdv_stage<T>(smem + is_buf * STAGE, a, is_d, DK_QC * is_c);
-      else dkdv_stage160<T>(lbase + is_buf * STAGE, a, is_d, DK_QC * is_c);
+      if constexpr (NKG == 8) dkdv_stage<T, SQ>(smem + is_buf * STAGE, a, is_d, is_c);
+      else dkdv_stage160<T, SQ>(lbase + is_buf * STAGE, a, is_d, is_c);
       after &= ~(15u << (4 * is_buf));
       ++inflight;
       if (++is_c == is_d.nch) {
         is_c = 0;
         is_item += istride;
         is_ok = is_item < iend;
-        if (is_ok) is_d = dk_decode<KT>(a, is_item);
+        if (is_ok) is_d = dk_decode<KT, SQ>(a, is_item);
       }
     }
     is_buf = is_buf == NS - 1 ? 0 : is_buf + 1;
@@ -376,7 +432,7 @@ __global__ __launch_bounds__(512, 2) void attn_dkdv_kernel(AttnDkdvArgs a) {
   int buf = 0;
 
   while (true) {
-    const DkItem d = dk_decode<KT>(a, item);
+    const DkItem d = dk_decode<KT, SQ>(a, item);
     const bool more = item + istride < iend;
     f32x4 acc[NKG][4];
 #pragma unroll
@@ -392,7 +448,9 @@ __global__ __launch_bounds__(512, 2) void attn_dkdv_kernel(AttnDkdvArgs a) {
       --inflight;
       lds_barrier();
       issue();
-      const int c0 = DK_QC * c;                         // first contraction index of the chunk
+      // first contraction index of the chunk (a merged dQ item: within its half's keys, so the
+      // last chunk of EACH sequence's key range is masked)
+      const int c0 = DK_QC * (SQ && c >= d.nch1 ? c - d.nch1 : c);
       const int clen = d.role == 2 ? a.Lk : a.Lq;       // contraction length
       F df[4];
       // the P / dS fragments in batches of KB groups (128 rows: one batch, read before the dO /
@@ -549,14 +607,19 @@ static int dkdv_plan(int Lq, int Lk, int64_t sdk_l, int64_t sdv_l, int64_t sdq_l
   return dkdv_cost(Lq, Lk, 160) < dkdv_cost(Lq, Lk, 128) ? 160 : 128;   // ties keep 128
 }
 
-template <typename T, int NKG>
-static void dkdv_launch(const AttnDkdvArgs& a, int grid, hipStream_t st) {
+template <typename T, int NKG, bool SQ>
+static void dkdv_launch_sq(const AttnDkdvArgs& a, int grid, hipStream_t st) {
   constexpr int lds = DkGeo<NKG>::LDS;
-  static bool once = ((void)hipFuncSetAttribute((const void*)attn_dkdv_kernel<T, NKG>,
+  static bool once = ((void)hipFuncSetAttribute((const void*)attn_dkdv_kernel<T, NKG, SQ>,
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds),
                       true);
   (void)once;
-  hipLaunchKernelGGL((attn_dkdv_kernel<T, NKG>), dim3(grid), dim3(512), (size_t)lds, st, a);
+  hipLaunchKernelGGL((attn_dkdv_kernel<T, NKG, SQ>), dim3(grid), dim3(512), (size_t)lds, st, a);
+}
+template <typename T, int NKG>
+static void dkdv_launch(const AttnDkdvArgs& a, int grid, hipStream_t st, bool sq) {
+  if (sq) dkdv_launch_sq<T, NKG, true>(a, grid, st);
+  else dkdv_launch_sq<T, NKG, false>(a, grid, st);
 }
 
 }  // namespace jmt
@@ -576,12 +639,14 @@ extern "C" int jmt_attn_dkdv_plan(int Lq, int Lk, int H, int64_t sdk_l, int64_t 
   return dkdv_plan(Lq, Lk, sdk_l, sdv_l, sdq_l, has_dq != 0);
 }
 
-extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const void* p,
-                             const void* ds, int64_t ldp, const void* go, int64_t sgo_l,
-                             int64_t sgo_n, const void* q, int64_t sq_l, int64_t sq_n,
-                             const void* k, int64_t sk_l, int64_t sk_n, void* dk, int64_t sdk_l,
-                             int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n, void* dq,
-                             int64_t sdq_l, int64_t sdq_n, void* stream) {
+// jmt_attn_dkdv (qs == NULL) and jmt_attn_dkdv_sq (qs: the packed query table of npair pairs;
+// merge: one dQ per shared query, qtab the table qs was packed from)
+static int dkdv_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* p, const void* ds,
+                     int64_t ldp, const void* go, int64_t sgo_l, int64_t sgo_n, const void* q,
+                     int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                     void* dk, int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l,
+                     int64_t sdv_n, void* dq, int64_t sdq_l, int64_t sdq_n, const QShare* qs,
+                     const int* qtab, int npair, int merge, void* stream) {
   constexpr int DK_KT = DkGeo<8>::KT;                  // the contract's tile: ldp, stride ranges
   if (N == 0 || Lk == 0) return JMT_OK;
   if (!((dt == JMT_BF16 || dt == JMT_F16) && dh == AT_DH))
@@ -620,6 +685,7 @@ extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const
                     (int64_t)Lq * ldp * 2 < (1LL << 31),
                 "jmt_attn_dkdv: Lq rows of dO / Q / P exceed 2 GiB");
   AttnDkdvArgs a = {};
+  if (qs) a.qs = *qs;
   a.p = p; a.ds = ds; a.go = go; a.q = q; a.k = k; a.dk = dk; a.dv = dv; a.dq = dq;
   a.ldp = ldp; a.sgo_l = sgo_l; a.sgo_n = sgo_n; a.sq_l = sq_l; a.sq_n = sq_n;
   a.sk_l = sk_l; a.sk_n = sk_n;
@@ -627,15 +693,69 @@ extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const
   a.sdq_l = sdq_l; a.sdq_n = sdq_n;
   a.Lq = Lq; a.Lk = Lk; a.H = H; a.nkt = nkt; a.nqd = nqd; a.ipn = 2 * nkt + nqd;
   a.nitems = N * H * a.ipn;
+  if (merge) {
+    // every pair is a first use with exactly one second use, or that second use: npair / 2
+    // groups of nqd merged dQ items + the two sequences' dV / dK items
+    int ng = 0;
+    for (int f = 0; f < npair; ++f) {
+      if (qtab[f] != f) continue;
+      int second = -1, uses = 0;
+      for (int j = 0; j < npair; ++j)
+        if (j != f && qtab[j] == f) { second = j; ++uses; }
+      if (uses != 1)
+        return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_dkdv_sq: merged dQ needs every query "
+                                              "used exactly twice (pair %d: %d more uses)",
+                         f, uses);
+      a.mg_first |= (uint32_t)f << (4 * ng);
+      a.mg_second |= (uint32_t)second << (4 * ng);
+      ++ng;
+    }
+    a.mrg = 1;
+    a.ipn = nqd + 4 * nkt;
+    a.nitems = ng * a.qs.spp * H * a.ipn;
+  }
   const int grid = dkdv_grid(a.nitems);
   hipStream_t st = as_stream(stream);
   if (kt == 160) {
-    if (dt == JMT_BF16) dkdv_launch<__bf16, 10>(a, grid, st);
-    else dkdv_launch<_Float16, 10>(a, grid, st);
+    if (dt == JMT_BF16) dkdv_launch<__bf16, 10>(a, grid, st, qs != nullptr);
+    else dkdv_launch<_Float16, 10>(a, grid, st, qs != nullptr);
   } else {
-    if (dt == JMT_BF16) dkdv_launch<__bf16, 8>(a, grid, st);
-    else dkdv_launch<_Float16, 8>(a, grid, st);
+    if (dt == JMT_BF16) dkdv_launch<__bf16, 8>(a, grid, st, qs != nullptr);
+    else dkdv_launch<_Float16, 8>(a, grid, st, qs != nullptr);
   }
   JMT_LAUNCH_CHECK("jmt_attn_dkdv");
   return JMT_OK;
+}
+
+extern "C" int jmt_attn_dkdv(int dt, int N, int H, int Lq, int Lk, int dh, const void* p,
+                             const void* ds, int64_t ldp, const void* go, int64_t sgo_l,
+                             int64_t sgo_n, const void* q, int64_t sq_l, int64_t sq_n,
+                             const void* k, int64_t sk_l, int64_t sk_n, void* dk, int64_t sdk_l,
+                             int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n, void* dq,
+                             int64_t sdq_l, int64_t sdq_n, void* stream) {
+  return dkdv_impl(dt, N, H, Lq, Lk, dh, p, ds, ldp, go, sgo_l, sgo_n, q, sq_l, sq_n, k, sk_l,
+                   sk_n, dk, sdk_l, sdk_n, dv, sdv_l, sdv_n, dq, sdq_l, sdq_n, nullptr, nullptr,
+                   0, 0, stream);
+}
+
+extern "C" int jmt_attn_dkdv_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* p,
+                                const void* ds, int64_t ldp, const void* go, int64_t sgo_l,
+                                int64_t sgo_n, const void* q, int64_t sq_l, int64_t sq_n,
+                                const void* k, int64_t sk_l, int64_t sk_n, void* dk,
+                                int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l,
+                                int64_t sdv_n, void* dq, int64_t sdq_l, int64_t sdq_n, int spp,
+                                const int* qtab, int npair, int merge_dq, void* stream) {
+  if (N == 0 || Lk == 0) return JMT_OK;
+  if (!((dt == JMT_BF16 || dt == JMT_F16) && dh == AT_DH))
+    return set_error(JMT_ERR_UNSUPPORTED,
+                     "jmt_attn_dkdv_sq: dtype %d / head dim %d not supported", dt, dh);
+  if (dq == nullptr)
+    return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_dkdv_sq: the tile-major form only (dq != "
+                                          "NULL: P / dS from jmt_attn_bwd_sq)");
+  QShare qs = {};
+  int rc = qshare_pack("jmt_attn_dkdv_sq", N, spp, qtab, npair, &qs);
+  if (rc != JMT_OK) return rc;
+  return dkdv_impl(dt, N, H, Lq, Lk, dh, p, ds, ldp, go, sgo_l, sgo_n, q, sq_l, sq_n, k, sk_l,
+                   sk_n, dk, sdk_l, sdk_n, dv, sdv_l, sdv_n, dq, sdq_l, sdq_n, &qs, qtab, npair,
+                   merge_dq != 0, stream);
 }

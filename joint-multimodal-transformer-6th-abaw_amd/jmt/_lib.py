@@ -105,6 +105,19 @@ _PROTOS = {
     "jmt_attn_dkdv": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp,
                               c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                               c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    # shared queries: the unshared signatures + (spp, qtab, npair[, merge_dq]) before the stream;
+    # jmt_attn_bwd_sq has no dq arguments (P / dS only)
+    "jmt_attn_fwd_sq": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
+                                c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_f,
+                                c_vp, c_int, C.POINTER(c_int), c_int, c_vp]),
+    "jmt_attn_bwd_sq": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
+                                c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
+                                c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_f, c_int,
+                                C.POINTER(c_int), c_int, c_vp]),
+    "jmt_attn_dkdv_sq": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64,
+                                 c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
+                                 c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_int,
+                                 C.POINTER(c_int), c_int, c_int, c_vp]),
     # the tile (128 / 160 rows) jmt_attn_dkdv takes: (Lq, Lk, H, sdk_l, sdv_l, sdq_l, has_dq)
     "jmt_attn_dkdv_plan": (c_int, [c_int, c_int, c_int, c_i64, c_i64, c_i64, c_int]),
     # dev switch outside include/jmt.h: 128 / 160 force the tile where it is valid, 0 the rule,

@@ -824,9 +824,32 @@ def _small_aligned(t, col, cd):
             and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0)
 
 
-def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol):
+def attn_shared_ok(q_src, k_src, v_src, E, H, qcol, kcol, vcol) -> bool:
+    """Whether attn_forward / attn_backward take `qshare` for these views (gradient buffers laid
+    out like the sources): the 16-bit fused kernels on the whole-row forward and the P / dS +
+    dK / dV / dQ backward, i.e. every condition under which attn_backward reaches its
+    `pds` branch, and Lq > 64.  Anything else keeps the unshared launches."""
+    cd = compute_dtype()
+    if cd == torch.float32:
+        return False
+    Lq, N = q_src.shape[0], q_src.shape[1]
+    Lk = k_src.shape[0]
+    dh = E // H
+    aligned = all(_small_aligned(t, c, cd)
+                  for t, c in ((q_src, qcol), (k_src, kcol), (v_src, vcol)))
+    if not aligned or ops.small_attn_ok(E, H, Lq, Lk) or ops.attn_short_ok(_dc(cd), dh, Lq, Lk):
+        return False
+    sq_l, sk_l, sv_l = q_src.stride(0), k_src.stride(0), v_src.stride(0)
+    return (ops.attn_sq_ok(_dc(cd), dh, Lq, Lk, sk_l, sv_l)
+            and ops.attn_dkdv_ok(N, H, Lq, Lk, dh, E, sq_l, sk_l, sv_l)
+            and ops.attn_pds_ok(Lq, Lk, sq_l, max(sk_l, sv_l), H))
+
+
+def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
     """softmax(Q K^T / sqrt(dh)) V on seq-first strided views (see AttnCoreFn).  Returns the
-    output (Lq, N, E) (memory order of q_src's rows) and the state attn_backward needs."""
+    output (Lq, N, E) (memory order of q_src's rows) and the state attn_backward needs.
+    qshare = (spp, qtab): sequence p spp + b reads the Q rows of sequence qtab[p] spp + b
+    (ops.attn_fwd_sq; the caller has asked attn_shared_ok)."""
     cd = compute_dtype()
     for t in (q_src, k_src, v_src):
         assert t.dtype == cd and t.stride(-1) == 1
@@ -847,6 +870,7 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol):
              ops.attn_short_ok(_dc(cd), dh, Lq, Lk))
     fused = "small" if small else ("short" if short else
                                    (cd != torch.float32 and ops.attn_supported(_dc(cd), dh)))
+    assert qshare is None or fused is True, "attn_forward: qshare on an unsupported shape"
     if small:
         # short sequences (SELF_ATTEN head, intra-modal fusion): one wave per sequence, the
         # fp32 probabilities (N*H*Lq*Lk floats) kept for the backward (small_attn.hip)
@@ -861,12 +885,14 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol):
         # one kernel: scores stay on chip (attn.hip); only lse is kept for the backward, which
         # recomputes the probabilities
         lse = torch.empty(N * H * Lq, dtype=torch.float32, device=dev)
-        (ops.attn_short_fwd if fused == "short" else ops.attn_fwd)(
+        (ops.attn_short_fwd if fused == "short" else
+         ops.attn_fwd_sq if qshare is not None else ops.attn_fwd)(
                      _dc(cd), N, H, Lq, Lk, dh,
                      _ptr(q_src, qcol), (q_src.stride(0), q_src.stride(1)),
                      _ptr(k_src, kcol), (k_src.stride(0), k_src.stride(1)),
                      _ptr(v_src, vcol), (v_src.stride(0), v_src.stride(1)),
-                     o.data_ptr(), (o.stride(0), o.stride(1)), scale, lse)
+                     o.data_ptr(), (o.stride(0), o.stride(1)), scale, lse,
+                     *(qshare if qshare is not None else ()))
         tensors = (q_src, k_src, v_src, None, o, lse)
     else:
         P = AttnCoreFn._probs(q_src, k_src, E, H, qcol, kcol, ldS, scale, cd)
@@ -880,9 +906,12 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol):
     return o, (tensors, (E, H, qcol, kcol, vcol, ldS, scale, cd, fused))
 
 
-def attn_backward(saved, go, dq, dk, dv):
+def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
     """Gradients of attn_forward written into dq / dk / dv (seq-first views laid out like the
-    sources; the same qcol/kcol/vcol column offsets; dq/dk/dv may be the same packed buffer)."""
+    sources; the same qcol/kcol/vcol column offsets; dq/dk/dv may be the same packed buffer).
+    qshare: as attn_forward's.  dQ is then still written per sequence, unless merge_dq: one
+    dQ = dS_i K_i + dS_j K_j per shared query in its first use's rows of dq, the second use's
+    rows left unwritten."""
     (q_src, k_src, v_src, P, o, lse), meta = saved
     E, H, qcol, kcol, vcol, ldS, scale, cd, fused = meta
     Lq, N = q_src.shape[0], q_src.shape[1]
@@ -940,6 +969,18 @@ def attn_backward(saved, go, dq, dk, dv):
             k_src, kcol, cd) and ops.attn_pds_ok(
             Lq, Lk, dq.stride(0), max(sk_l, sv_l), H)
         dq_args = (_ptr(dq, qcol), (dq.stride(0), dq.stride(1)))
+        if qshare is not None:
+            assert pds, "attn_backward: qshare on an unsupported shape"
+            ops.attn_bwd_sq(_dc(cd), N, H, Lq, Lk, dh, go.data_ptr(), (so_l, so_n),
+                            o.data_ptr(), (o.stride(0), o.stride(1)),
+                            _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
+                            _ptr(v_src, vcol), (sv_l, sv_n), lse, P, dS, ldp, scale, *qshare)
+            ops.attn_dkdv_sq(_dc(cd), N, H, Lq, Lk, dh, P, dS, ldp, go.data_ptr(), (so_l, so_n),
+                             _ptr(q_src, qcol), (sq_l, sq_n), _ptr(dk, kcol),
+                             (dk.stride(0), dk.stride(1)), _ptr(dv, vcol),
+                             (dv.stride(0), dv.stride(1)), _ptr(k_src, kcol), (sk_l, sk_n),
+                             *dq_args, *qshare, merge_dq)
+            return
         ops.attn_bwd(_dc(cd), N, H, Lq, Lk, dh, go.data_ptr(), (so_l, so_n),
                      o.data_ptr(), (o.stride(0), o.stride(1)),
                      _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
@@ -950,6 +991,7 @@ def attn_backward(saved, go, dq, dk, dv):
                       (dk.stride(0), dk.stride(1)), _ptr(dv, vcol), (dv.stride(0), dv.stride(1)),
                       *((_ptr(k_src, kcol), (sk_l, sk_n)) + dq_args if pds else ()))
         return
+    assert qshare is None, "attn_backward: qshare on an unsupported shape"
     bS = (H * Lq * ldS, Lq * ldS)
     dS = torch.empty(N * H * Lq * ldS, dtype=cd, device=dev)
     if fused:

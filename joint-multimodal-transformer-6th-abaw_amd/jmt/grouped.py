@@ -11,7 +11,8 @@ its own nn.Parameters, so state_dict keys are untouched), the attention core run
 sequences in one launch, and the six cross-attentions likewise over 6 stacked (query, key) pairs.
 The backward of each group is written out explicitly: gradients that the reference's autograd
 would sum from several uses (a stream's encoder output feeds 4 projections) are produced by ONE
-K-concatenated dgrad GEMM per stream (K = 6E), and weight gradients are accumulated in place
+K-concatenated dgrad GEMM per stream (K = 6E; 5E with one dQ per shared query, see
+CrossAttention6Fn), and weight gradients are accumulated in place
 (beta = 1) by batched wgrad GEMMs — no autograd adds, no cross-stream synchronisation, and a
 single HIP stream that captures into a hipGraph (jmt/graph.py).
 
@@ -30,7 +31,7 @@ from torch.autograd import Function
 
 from . import ops, streams
 from .functional import (_dc, _grad_buffer, _grad_done, _ptr, attn_backward, attn_forward,
-                         compute_dtype, weight_as, wgrad_scope)
+                         attn_shared_ok, compute_dtype, weight_as, wgrad_scope)
 
 _enabled = {"on": os.environ.get("JMT_GROUPED", "1") != "0"}
 # the cross-attention backward's three stream-gradient GEMMs on branch streams: measured
@@ -54,17 +55,20 @@ def set_enabled(on: bool) -> None:
 
 # ------------------------------------------------------------------------- grouped GEMMs
 def _gemm_fwd(a_ptrs: Sequence[int], lda: int, sA: int, rows: int, K: int, Ws, r0: int, n: int,
-              bs, c_ptr: int, ldc: int, sC: int, c_dt: int, cd, dev, relu: bool = False):
+              bs, c_ptr, ldc: int, sC: int, c_dt: int, cd, dev, relu: bool = False):
     """C[g] = A[g] (rows x K) . W_g[r0:r0+n]^T + b_g[r0:r0+n]  for g < len(Ws), one launch.
-    A is strided (a_ptrs = [base], sA) or a per-group pointer table (len(a_ptrs) == len(Ws))."""
+    A is strided (a_ptrs = [base], sA) or a per-group pointer table (len(a_ptrs) == len(Ws));
+    C is strided (c_ptr, sC) or, with a list of len(Ws) pointers, a per-group table."""
     Wc = [weight_as(W, cd) for W in Ws]
     Kin = Wc[0].shape[1]
     table = len(a_ptrs) > 1
+    c_tab = isinstance(c_ptr, (list, tuple))
     ops.gemm(M=rows, N=n, K=K, ab_dtype=_dc(cd), c_dtype=c_dt,
              a=list(a_ptrs), lda=lda, a_kmajor=True, a_mode=1 if table else 0,
              sA=(0 if table else sA, 0),
              b=[_ptr(w, r0 * Kin) for w in Wc], ldb=Kin, b_kmajor=True, b_mode=1,
-             c=[c_ptr], ldc=ldc, sC=(sC, 0), batch0=len(Ws),
+             c=list(c_ptr) if c_tab else [c_ptr], ldc=ldc, c_mode=1 if c_tab else 0,
+             sC=(0 if c_tab else sC, 0), batch0=len(Ws),
              bias_tab=[b[r0:r0 + n] for b in bs] if bs is not None else None, bias_mode=1,
              relu=relu, device=dev)
 
@@ -615,6 +619,24 @@ def mha_params(mha) -> List[torch.Tensor]:
     return [mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias]
 
 
+# Pairs that apply the same module to the same query stream (CROSS_PAIRS: 0 and 3, 1 and 5,
+# 2 and 4) have the same query projection.  It is computed once, the attention kernels read it
+# from the first use's rows of QKV (JMT_CA_SHARED_Q=0: every pair projects its own, the launches
+# of before), and the two uses' query gradients leave the chip as ONE dQ = dS_i K_i + dS_j K_j
+# (JMT_CA_DQ_MERGE=0: one dQ per pair, summed by the K-concatenated GEMMs downstream; bitwise
+# the unshared results).
+_shared_q = {"on": os.environ.get("JMT_CA_SHARED_Q", "1") != "0",
+             "merge": os.environ.get("JMT_CA_DQ_MERGE", "1") != "0"}
+
+
+def shared_query_table(pairs):
+    """qtab[i] = the first pair with pair i's (module, query stream); None without duplicates."""
+    first, qtab = {}, []
+    for i, (m, q, _) in enumerate(pairs):
+        qtab.append(first.setdefault((m, q), i))
+    return qtab if any(t != i for i, t in enumerate(qtab)) and len(pairs) <= 8 else None
+
+
 class CrossAttention6Fn(Function):
     """The six key-is-value cross-attentions of mm_multi_transformers.py:142-167 on the stacked
     encoder outputs Y (3, B, T, E) -> O6 (6, B, T, E) in the reference's concatenation order
@@ -634,26 +656,40 @@ class CrossAttention6Fn(Function):
         QKV = torch.empty(NP, B, T, 3 * E, dtype=cd, device=dev)
         in_w = [M[m][0] for m, _, _ in pairs]
         in_b = [M[m][1] for m, _, _ in pairs]
-        # queries (each module's query projection is evaluated for both of its calls, exactly as
-        # the reference does) and packed key/values, one launch each
-        _gemm_fwd([Y[q].data_ptr() for _, q, _ in pairs], E, 0, R, E, in_w, 0, E, in_b,
-                  QKV.data_ptr(), 3 * E, R * 3 * E, cdt, cd, dev)
+        sf = QKV.view(NP * B, T, 3 * E).permute(1, 0, 2)
+        qtab = shared_query_table(pairs) if _shared_q["on"] else None
+        if qtab is not None and not attn_shared_ok(sf, sf, sf, E, H, 0, E, 2 * E):
+            qtab = None
+        # queries and packed key/values, one launch each.  Shared queries: the projection of the
+        # first use only (the q columns of the other uses' rows of QKV stay unused); otherwise
+        # each module's query projection is evaluated for both of its calls, as the reference does
+        if qtab is not None:
+            fu = [i for i, t in enumerate(qtab) if t == i]
+            c_q = [_ptr(QKV, i * R * 3 * E) for i in fu]
+            if _consecutive(fu):
+                c_q = c_q[0]
+            _gemm_fwd([Y[pairs[i][1]].data_ptr() for i in fu], E, 0, R, E,
+                      [in_w[i] for i in fu], 0, E, [in_b[i] for i in fu], c_q, 3 * E,
+                      R * 3 * E, cdt, cd, dev)
+        else:
+            _gemm_fwd([Y[q].data_ptr() for _, q, _ in pairs], E, 0, R, E, in_w, 0, E, in_b,
+                      QKV.data_ptr(), 3 * E, R * 3 * E, cdt, cd, dev)
         _gemm_fwd([Y[k].data_ptr() for _, _, k in pairs], E, 0, R, E, in_w, E, 2 * E, in_b,
                   _ptr(QKV, E), 3 * E, R * 3 * E, cdt, cd, dev)
-        sf = QKV.view(NP * B, T, 3 * E).permute(1, 0, 2)
-        o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E)
+        qshare = (B, qtab) if qtab is not None else None
+        o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, qshare=qshare)
         O = o.permute(1, 0, 2)                                   # (NP*B, T, E) memory
         O6 = torch.empty(NP, B, T, E, dtype=cd, device=dev)
         _gemm_fwd([O.data_ptr()], E, R * E, R, E, [M[m][2] for m, _, _ in pairs], 0, E,
                   [M[m][3] for m, _, _ in pairs], O6.data_ptr(), E, R * E, cdt, cd, dev)
         ctx.params = params
         ctx.state = (Y, QKV, asaved, O)
-        ctx.meta = (pairs, S, B, T, E, cd)
+        ctx.meta = (pairs, S, B, T, E, cd, qtab)
         return O6
 
     @staticmethod
     def backward(ctx, dO6):
-        pairs, S, B, T, E, cd = ctx.meta
+        pairs, S, B, T, E, cd, qtab = ctx.meta
         Y, QKV, asaved, O = ctx.state
         params = ctx.params
         M = [params[4 * m:4 * m + 4] for m in range(len(params) // 4)]
@@ -686,6 +722,12 @@ class CrossAttention6Fn(Function):
             h0 = list(halves[0])
             ms = [pairs[i][0] for i in h0]
             h1 = [next(j for j in halves[1] if pairs[j][0] == m) for m in ms]
+        # one dQ per shared query (in the first use's q columns of dQKV; the second use's stay
+        # unwritten): when every query is used exactly twice and, for the K-concatenated weight
+        # gradients, the two uses of every module are the two uses of one query
+        merge = (qtab is not None and _shared_q["merge"] and
+                 all(qtab.count(i) == 2 for i in set(qtab)) and
+                 (not kcat or all(qtab[i] == i and qtab[j] == i for i, j in zip(h0, h1))))
 
         def out_proj_grads():
             if kcat:
@@ -718,7 +760,8 @@ class CrossAttention6Fn(Function):
         # attention core -> packed dQKV (NP, B, T, 3E)
         dQKV = torch.empty(NP, B, T, 3 * E, dtype=cd, device=dev)
         dsf = dQKV.view(NP * B, T, 3 * E).permute(1, 0, 2)
-        attn_backward(asaved, dO.view(NP * B, T, E).permute(1, 0, 2), dsf, dsf, dsf)
+        attn_backward(asaved, dO.view(NP * B, T, E).permute(1, 0, 2), dsf, dsf, dsf,
+                      qshare=(B, qtab) if qtab is not None else None, merge_dq=merge)
 
         # in_proj weight gradients (side stream, overlapping the stream dgrads): query rows
         # [0, E) from the query stream, key/value rows [E, 3E) from the key stream
@@ -731,10 +774,17 @@ class CrossAttention6Fn(Function):
                 # the query-row and key / value-row launches sit next to each other: one
                 # grouped launch (their rows of W.grad / b.grad are disjoint)
                 with wgrad_scope():
-                    fq = _gemm_wgrad_kcat(seg(0), 3 * E,
-                                          [[Y[pairs[i][1]].data_ptr(), Y[pairs[j][1]].data_ptr()]
-                                           for i, j in zip(h0, h1)], E, R, E, ws, 0, cd, dev,
-                                          bs=bs)
+                    if merge:
+                        # the merged dQ against the query stream: a plain problem over K = B T
+                        fq = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E) for i in h0], 3 * E, 0,
+                                         [Y[pairs[i][1]].data_ptr() for i in h0], E, 0, R, E, ws,
+                                         0, cd, dev, bs=bs)
+                    else:
+                        fq = _gemm_wgrad_kcat(seg(0), 3 * E,
+                                              [[Y[pairs[i][1]].data_ptr(),
+                                                Y[pairs[j][1]].data_ptr()]
+                                               for i, j in zip(h0, h1)], E, R, E, ws, 0, cd, dev,
+                                              bs=bs)
                     fkv = _gemm_wgrad_kcat(seg(E), 3 * E,
                                            [[Y[pairs[i][2]].data_ptr(), Y[pairs[j][2]].data_ptr()]
                                             for i, j in zip(h0, h1)], E, R, 2 * E, ws, E, cd, dev,
@@ -743,12 +793,34 @@ class CrossAttention6Fn(Function):
                     assert not fq, "query-row bias sums fused without the key / value rows"
                     for m, i, j in zip(ms, h0, h1):
                         _bias_grad(dQKV[i], 3 * E, R, 3 * E, M[m][1], 0)
-                        _bias_grad(dQKV[j], 3 * E, R, 3 * E, M[m][1], 0)
+                        if merge:       # the second use has key / value columns only
+                            _bias_grad(dQKV[j].view(R, 3 * E)[:, E:], 3 * E, R, 2 * E, M[m][1], E)
+                        else:
+                            _bias_grad(dQKV[j], 3 * E, R, 3 * E, M[m][1], 0)
                 return
             rest = []
             for h in halves:
                 ws = [M[pairs[i][0]][0] for i in h]
                 bs = [M[pairs[i][0]][1] for i in h]
+                if merge:
+                    # query rows from the pairs that hold a (merged) dQ only
+                    hq = [i for i in h if qtab[i] == i]
+                    with wgrad_scope():
+                        fq = not hq or _gemm_wgrad(
+                            [_ptr(dQKV, i * R * 3 * E) for i in hq], 3 * E, 0,
+                            [Y[pairs[i][1]].data_ptr() for i in hq], E, 0, R, E,
+                            [M[pairs[i][0]][0] for i in hq], 0, cd, dev,
+                            bs=[M[pairs[i][0]][1] for i in hq])
+                        fkv = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E + E) for i in h], 3 * E, 0,
+                                          [Y[pairs[i][2]].data_ptr() for i in h], E, 0, R, 2 * E,
+                                          ws, E, cd, dev, bs=bs if fq else None)
+                    if not (fq and fkv):
+                        assert not (fq and hq), "query-row bias sums fused without the others"
+                        for i in h:
+                            c0 = 0 if i in hq else E
+                            _bias_grad(dQKV[i].view(R, 3 * E)[:, c0:], 3 * E, R, 3 * E - c0,
+                                       M[pairs[i][0]][1], c0)
+                    continue
                 with wgrad_scope():
                     fq = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E) for i in h], 3 * E, 0,
                                      [Y[pairs[i][1]].data_ptr() for i in h], E, 0, R, E, ws, 0,
@@ -769,7 +841,8 @@ class CrossAttention6Fn(Function):
 
         streams.run_side(in_proj_grads, reads=(dQKV, Y))
         # stream gradients: every use of stream s (as a query: rows [0,E) of W_in; as a key /
-        # value: rows [E,2E) and [2E,3E)) is one K-segment of ONE dgrad GEMM (K = nseg * E)
+        # value: rows [E,2E) and [2E,3E)) is one K-segment of ONE dgrad GEMM (K = nseg * E); a
+        # merged dQ is one segment for both of its uses
         dY = torch.zeros(S, B, T, E, dtype=cd, device=dev) if any(
             not any(q == s or k == s for _, q, k in pairs) for s in range(S)) else \
             torch.empty(S, B, T, E, dtype=cd, device=dev)
@@ -780,7 +853,7 @@ class CrossAttention6Fn(Function):
             for i, (m, q, k) in enumerate(pairs):
                 Wc = weight_as(M[m][0], cd)
                 keep.append(Wc)
-                if q == s:
+                if q == s and not (merge and qtab[i] != i):
                     a_ptrs.append(_ptr(dQKV, i * R * 3 * E))
                     b_ptrs.append(_ptr(Wc, 0))
                 if k == s:

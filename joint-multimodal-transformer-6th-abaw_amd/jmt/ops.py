@@ -481,6 +481,70 @@ def attn_dkdv(dtype, N, H, Lq, Lk, dh, p, ds, ldp, go_ptr, sgo, q_ptr, sq, dk_pt
                                       2 * Lq * attn_dkdv_ldp(Lk) * es + extra)}, launch)
 
 
+# ---- shared queries (jmt_attn_*_sq): sequence n = p spp + b reads the Q of sequence
+# qtab[p] spp + b.  The launch records keep the unshared families and algorithmic counts.
+def _qtab(qtab):
+    return (C.c_int * len(qtab))(*qtab), len(qtab)
+
+
+def attn_fwd_sq(dtype, N, H, Lq, Lk, dh, q_ptr, sq, k_ptr, sk, v_ptr, sv, o_ptr, so, scale, lse,
+                spp, qtab):
+    """attn_fwd with shared queries (the whole-row kernel: Lq > 64)."""
+    tab, npair = _qtab(qtab)
+    launch = lambda: _lib.call("jmt_attn_fwd_sq", dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
+                               k_ptr, sk[0], sk[1], v_ptr, sv[0], sv[1], o_ptr, so[0], so[1],
+                               scale, lse.data_ptr() if lse is not None else None, spp, tab,
+                               npair, stream())
+    es = 4 if dtype == F32 else 2
+    _hooked({"family": "attn_fwd", "flops": 4.0 * N * H * Lq * Lk * dh, "shared_q": True,
+             "bytes": float(N * H) * ((2 * Lq + 2 * Lk) * dh * es + 4 * Lq)}, launch)
+
+
+def attn_bwd_sq(dtype, N, H, Lq, Lk, dh, go_ptr, sgo, o_ptr, so, q_ptr, sq, k_ptr, sk, v_ptr, sv,
+                lse, p, ds, ldp, scale, spp, qtab):
+    """attn_bwd's P / dS form (dq_ptr None) with shared queries."""
+    tab, npair = _qtab(qtab)
+    launch = lambda: _lib.call("jmt_attn_bwd_sq", dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
+                               sgo[1], o_ptr, so[0], so[1], q_ptr, sq[0], sq[1], k_ptr, sk[0],
+                               sk[1], v_ptr, sv[0], sv[1], lse.data_ptr(), p.data_ptr(),
+                               ds.data_ptr(), ldp, scale, spp, tab, npair, stream())
+    es = 4 if dtype == F32 else 2
+    lw = -(-Lk // 32) * 32
+    _hooked({"family": "attn_bwd", "flops": 4.0 * N * H * Lq * Lk * dh, "shared_q": True,
+             "bytes": float(N * H) * ((3 * Lq + 2 * Lk) * dh * es + 4 * Lq +
+                                      2 * Lq * lw * es)}, launch)
+
+
+def attn_dkdv_sq(dtype, N, H, Lq, Lk, dh, p, ds, ldp, go_ptr, sgo, q_ptr, sq, dk_ptr, sdk, dv_ptr,
+                 sdv, k_ptr, sk, dq_ptr, sdq, spp, qtab, merge_dq):
+    """attn_dkdv (with dQ) on shared queries; merge_dq: one dQ = dS_i K_i + dS_j K_j per query,
+    in the first use's rows of dq (the second use's rows are left unwritten)."""
+    tab, npair = _qtab(qtab)
+    launch = lambda: _lib.call("jmt_attn_dkdv_sq", dtype, N, H, Lq, Lk, dh, p.data_ptr(),
+                               ds.data_ptr(), ldp, go_ptr, sgo[0], sgo[1], q_ptr, sq[0], sq[1],
+                               k_ptr, sk[0], sk[1], dk_ptr, sdk[0], sdk[1], dv_ptr, sdv[0],
+                               sdv[1], dq_ptr, sdq[0], sdq[1], spp, tab, npair, int(merge_dq),
+                               stream())
+    es = 4 if dtype == F32 else 2
+    nq = N // 2 if merge_dq else N        # dQ tensors written
+    extra = (Lk + Lq) * dh * es + Lq * (-(-Lk // 32) * 32) * es
+    _hooked({"family": "attn_dkdv", "flops": 6.0 * N * H * Lq * Lk * dh, "shared_q": True,
+             "merge_dq": bool(merge_dq),
+             "bytes": float(N * H) * ((2 * Lq + 2 * Lk) * dh * es +
+                                      2 * Lq * attn_dkdv_ldp(Lk) * es + extra) -
+                      float((N - nq) * H) * Lq * dh * es}, launch)
+
+
+def attn_sq_ok(dtype, dh, Lq, Lk, sk_l, sv_l) -> bool:
+    """Host-side mirror of what the *_sq entry points take: the 16-bit fused kernels, the
+    whole-row forward (Lq > 64, Lk K / V rows within 32-bit byte offsets) and the P / dS +
+    dK / dV / dQ pair of kernels switched on."""
+    lim = 1 << 31
+    return (dtype != F32 and attn_supported(dtype, dh) and _attn_dkdv["on"] and _attn_pds["on"]
+            and os.environ.get("JMT_ATTN_FWD_ROWS", "1") != "0"
+            and Lq > 64 and Lk * sk_l * 2 < lim and Lk * sv_l * 2 < lim)
+
+
 def attn_short_ok(dtype: int, dh: int, Lq: int, Lk: int) -> bool:
     """Shapes the one-block-per-sequence fused kernels cover (jmt_attn_short_*: 16-bit, dh = 512,
     Lq, Lk <= 32); off with JMT_ATTN_FUSED=0 or JMT_ATTN_SHORT=0 (A/B switch)."""
