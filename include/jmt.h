@@ -98,6 +98,17 @@ typedef struct jmt_gemm_desc {
 } jmt_gemm_desc;
 
 int jmt_gemm(const jmt_gemm_desc* desc, void* stream);
+/* jmt_gemm with the epilogue's beta * C operand read from another buffer (round 11; added to
+ * ABI 7, nothing else changes): c_in is a table parallel to desc->c (same c_mode, batch strides
+ * and dtype; 16-B aligned entries) with its own leading dimension ldcin (a multiple of 8
+ * elements, >= N), and C is only written.  An accumulating input gradient dX = dS + dY . W can
+ * so leave dS intact for a weight gradient that reads it later.  The launch and the result's
+ * bits are those of jmt_gemm on a C preloaded with c_in's contents (c_in == c is jmt_gemm).
+ * 16-bit C without split-K only: fp32 C or desc->splits > 1 return JMT_ERR_UNSUPPORTED;
+ * beta == 0, a NULL or short table or a misaligned ldcin JMT_ERR_ARG.  jmt_gemm_grouped's
+ * problems (fp32 C) have no such operand. */
+int jmt_gemm_cin(const jmt_gemm_desc* desc, const void* const* c_in, int n_c_in, int64_t ldcin,
+                 void* stream);
 size_t jmt_gemm_workspace_bytes(int M, int N, int batch, int splits);
 /* split-K factor jmt_gemm's planner picks for this problem (1 = no split).  jmt_gemm chooses the
  * block tile (128x128 or 256x256) from the same cost model: waves x (tile FLOPs / per-block MFMA
@@ -115,14 +126,14 @@ int jmt_gemm_trace_read(uint64_t* host, int nblocks);
  * launch.  Each problem is a jmt_gemm_desc of the form the training step's weight gradients
  * take: 16-bit A and B (one dtype and one majorness per group), fp32 C with any alpha / beta,
  * M and N multiples of 256, K a multiple of 64 (>= 256), batch1 = 1, operand modes 0, 1 and 3,
- * optional dbias_tab (NULL entries allowed; MN-major A and B, K >= 512).  bias, relu, aux, fp32
+ * optional dbias_tab (NULL entries allowed; MN-major A and B).  bias, relu, aux, fp32
  * operands, other sizes or a 16-bit C return JMT_ERR_UNSUPPORTED before anything is launched
  * (the caller runs jmt_gemm on that problem).  desc.workspace / dbias_ws are ignored: the group
  * shares `workspace` (jmt_gemm_grouped_workspace_bytes, 16-B aligned).
  * desc.splits: 0 lets the group's planner choose — one target item length for the whole group,
  * so that the items of all problems fill the persistent grid in whole rounds; >= 1 forces that
- * problem's split count.  A problem with one split writes C in the GEMM's epilogue and takes no
- * slab.  jmt_gemm_grouped_plan reports the split counts (splits_out[n]); a problem's C and row
+ * problem's split count.  A problem with one split writes C — and, with a dbias_tab, its row sums
+ * — in the GEMM's epilogue, takes no slab and no block of the reduce.  jmt_gemm_grouped_plan reports the split counts (splits_out[n]); a problem's C and row
  * sums have the bits of jmt_gemm on it alone, on the split-K ping-pong kernel, at that count. */
 int jmt_gemm_grouped(const jmt_gemm_desc* descs, int n, void* workspace, size_t ws_bytes,
                      void* stream);

@@ -68,6 +68,40 @@ int main() {
   expect_msg("gemm dbias table > 8", "dbias table");
   d.n_dbias = 0;
   expect_err("gemm null desc", jmt_gemm(nullptr, nullptr));
+  // jmt_gemm_cin: the beta * C operand from another table — refused before any launch
+  {
+    const void* cin[1] = {algn};
+#define CIN_ERR(what, code, needle, set, reset)                                  \
+    do {                                                                         \
+      set;                                                                       \
+      const int rc_ = jmt_gemm_cin(&d, cin, 1, 128, nullptr);                    \
+      expect_err(what, rc_);                                                     \
+      expect_msg(what, needle);                                                  \
+      if (rc_ != code) {                                                         \
+        fprintf(stderr, "FAIL %s: rc=%d, not %d\n", what, rc_, (int)code);       \
+        ++g_fail;                                                                \
+      }                                                                          \
+      reset;                                                                     \
+    } while (0)
+    d.c_dtype = JMT_BF16; d.beta = 1.f;
+    CIN_ERR("gemm_cin fp32 C", JMT_ERR_UNSUPPORTED, "16-bit C", d.c_dtype = JMT_F32,
+            d.c_dtype = JMT_BF16);
+    CIN_ERR("gemm_cin forced splits", JMT_ERR_UNSUPPORTED, "split-K", d.splits = 2, d.splits = 0);
+    CIN_ERR("gemm_cin beta 0", JMT_ERR_ARG, "beta == 0", d.beta = 0.f, d.beta = 1.f);
+    CIN_ERR("gemm_cin null entry", JMT_ERR_ARG, "c_in[0]", cin[0] = nullptr, cin[0] = algn);
+    CIN_ERR("gemm_cin misaligned entry", JMT_ERR_ARG, "c_in[0]", cin[0] = misal, cin[0] = algn);
+#undef CIN_ERR
+    expect_err("gemm_cin null table", jmt_gemm_cin(&d, nullptr, 1, 128, nullptr));
+    expect_msg("gemm_cin null table", "c_in table");
+    d.c_mode = 1; d.batch0 = 2; d.n_c = 2; d.c[1] = algn;
+    expect_err("gemm_cin short table", jmt_gemm_cin(&d, cin, 1, 128, nullptr));
+    expect_msg("gemm_cin short table", "c_in table");
+    d.c_mode = 0; d.batch0 = 1; d.n_c = 1;
+    expect_err("gemm_cin misaligned ldcin", jmt_gemm_cin(&d, cin, 1, 132, nullptr));
+    expect_msg("gemm_cin misaligned ldcin", "ldcin");
+    expect_err("gemm_cin null desc", jmt_gemm_cin(nullptr, cin, 1, 128, nullptr));
+    d.c_dtype = JMT_F32; d.beta = 0.f;
+  }
   size_t ws = 0;
   for (int m = 1; m <= 1 << 16; m *= 7)
     for (int s = 1; s <= 256; s *= 4) ws += jmt_gemm_workspace_bytes(m, 512, 3, s);
@@ -127,6 +161,20 @@ int main() {
     gd[0].c[0] = algn; gd[0].n_dbias = 1; gd[0].dbias_tab[0] = nullptr;
     expect_err("grouped dbias null entry", jmt_gemm_grouped(gd, 2, algn, (size_t)1 << 40, nullptr));
     expect_msg("grouped dbias null entry", "every dbias_tab entry");
+    // row sums no longer force a second split: the plan with a dbias table on both problems
+    // is the plan without, and a forced single split is taken
+    int sp_rs[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) { gd[i].n_dbias = 1; gd[i].dbias_tab[0] = (float*)algn; }
+    int rc_rs = jmt_gemm_grouped_plan(gd, 2, sp_rs);
+    const bool same = rc_rs == JMT_OK && sp_rs[0] == sp[0] && sp_rs[1] == sp[1];
+    gd[1].splits = 1;
+    rc_rs = jmt_gemm_grouped_plan(gd, 2, sp_rs);
+    if (!same || rc_rs != JMT_OK || sp_rs[1] != 1 ||
+        jmt_gemm_grouped_workspace_bytes(gd, 2) == 0) {
+      fprintf(stderr, "FAIL grouped plan with row sums: %s (splits %d %d vs %d %d)\n",
+              jmt_last_error(), sp_rs[0], sp_rs[1], sp[0], sp[1]);
+      ++g_fail;
+    }
   }
 
   // row ops

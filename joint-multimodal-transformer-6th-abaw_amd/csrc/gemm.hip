@@ -103,10 +103,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, const GemmWor
   const bool partial = p.splits > 1;
   const float* biasp = p.n_bias > 0 ? p.bias_tab[b0] : p.bias;
   O* cp;
+  const O* cinp = nullptr;      // the beta * C operand (GemmParams::cin_ptr: C itself, or c_in)
   int64_t cbase;
   float alpha = p.alpha, beta = p.beta;
   int bias_mode = p.bias_mode, relu = p.relu;
   int64_t ldc = p.ldc;
+  const int64_t ldcin = p.ldcin;
   const O* auxp = partial ? nullptr : (const O*)p.aux;
   if (partial) {   // raw partial sums: no epilogue ops, row stride N
     const int nb = p.batch0 * p.batch1;
@@ -116,9 +118,11 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, const GemmWor
   } else {
     if (p.c_mode == 1) {
       cp = (O*)p.c_ptr[b0];
+      cinp = (const O*)p.cin_ptr[b0];
       cbase = (int64_t)b1 * p.sC1;
     } else {
       cp = (O*)p.c_ptr[0];
+      cinp = (const O*)p.cin_ptr[0];
       cbase = (int64_t)b0 * p.sC0 + (int64_t)b1 * p.sC1;
     }
   }
@@ -157,7 +161,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, const GemmWor
         if (beta != 0.f) {
 #pragma unroll
           for (int j = 0; j < C::TN; ++j)
-            load4_guard(cp + rowo, n0 + wn * C::WTN + 16 * j + 4 * g, p.N, true, cin[j]);
+            load4_guard(cinp + cbase + (int64_t)m * ldcin, n0 + wn * C::WTN + 16 * j + 4 * g, p.N,
+                        true, cin[j]);
         }
         if (auxp) {
 #pragma unroll
@@ -228,7 +233,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, const GemmWor
       float cin[C::TN][4], ain[C::TN][4];
       if (beta != 0.f) {
 #pragma unroll
-        for (int j = 0; j < C::TN; ++j) load4_guard(cp + rowo, n0 + wn * C::WTN + 16 * j + cq, p.N, vec4, cin[j]);
+        for (int j = 0; j < C::TN; ++j)
+          load4_guard(cinp + cbase + (int64_t)m * ldcin, n0 + wn * C::WTN + 16 * j + cq, p.N, vec4,
+                      cin[j]);
       }
       if (auxp) {
 #pragma unroll
@@ -699,7 +706,10 @@ extern "C" size_t jmt_gemm_workspace_bytes(int M, int N, int batch, int splits) 
   return (size_t)splits * (size_t)batch * (size_t)M * (size_t)N * sizeof(float);
 }
 
-extern "C" int jmt_gemm(const jmt_gemm_desc* d, void* stream) {
+// jmt_gemm (cin == false: the epilogue's beta * C operand is C) and jmt_gemm_cin (a table c_in
+// parallel to d->c with its own leading dimension) — the same launch, one load address apart
+static int gemm_run(const jmt_gemm_desc* d, bool cin, const void* const* c_in, int n_c_in,
+                    int64_t ldcin, void* stream) {
   JMT_CHECK_ARG(d != nullptr, "jmt_gemm: null descriptor");
   const int dt = d->ab_dtype;
   JMT_CHECK_ARG(dt == JMT_F32 || dt == JMT_BF16 || dt == JMT_F16, "jmt_gemm: bad ab_dtype %d", dt);
@@ -797,6 +807,25 @@ extern "C" int jmt_gemm(const jmt_gemm_desc* d, void* stream) {
     p.c_vec8 = cv8 ? 1 : 0;
   }
 
+  for (int i = 0; i < MAXP; ++i) p.cin_ptr[i] = p.c_ptr[i];
+  p.ldcin = d->ldc;
+  if (cin) {
+    JMT_CHECK_ARG(d->beta != 0.f, "jmt_gemm_cin: beta == 0 reads no C operand");
+    JMT_CHECK_ARG(c_in != nullptr && n_c_in >= (d->c_mode == 1 ? batch0 : 1) && n_c_in <= MAXP,
+                  "jmt_gemm_cin: c_in table null or shorter than C's");
+    for (int i = 0; i < n_c_in; ++i)
+      JMT_CHECK_ARG(c_in[i] != nullptr && ((uintptr_t)c_in[i] & 15) == 0,
+                    "jmt_gemm_cin: c_in[%d] null or not 16-B aligned", i);
+    JMT_CHECK_ARG(ldcin >= d->N && ldcin % 8 == 0,
+                  "jmt_gemm_cin: ldcin must be a multiple of 8 elements, at least N");
+    if (d->c_dtype == JMT_F32 || dt == JMT_F32)
+      return set_error(JMT_ERR_UNSUPPORTED, "jmt_gemm_cin: 16-bit C only");
+    if (d->splits > 1)
+      return set_error(JMT_ERR_UNSUPPORTED, "jmt_gemm_cin: split-K reduces into C itself");
+    for (int i = 0; i < MAXP; ++i) p.cin_ptr[i] = i < n_c_in ? c_in[i] : nullptr;
+    p.ldcin = ldcin;
+  }
+
   int splits = d->splits < 1 ? 1 : d->splits;
   // each split owns whole K-tiles, so a K-concat segment boundary never cuts a tile
   int kps = ((d->K + splits - 1) / splits + BKE - 1) / BKE * BKE;
@@ -889,11 +918,21 @@ extern "C" int jmt_gemm(const jmt_gemm_desc* d, void* stream) {
   return JMT_OK;
 }
 
+extern "C" int jmt_gemm(const jmt_gemm_desc* d, void* stream) {
+  return gemm_run(d, false, nullptr, 0, 0, stream);
+}
+
+extern "C" int jmt_gemm_cin(const jmt_gemm_desc* d, const void* const* c_in, int n_c_in,
+                            int64_t ldcin, void* stream) {
+  return gemm_run(d, true, c_in, n_c_in, ldcin, stream);
+}
+
 // ------------------------------------------------------------------ grouped weight gradients
 // jmt_gemm_grouped (gemm_persist.hip: gemm_group_kernel, group_reduce_kernel).  Planning is a
 // pure host function: ONE target item length L (K-tiles) for the whole group, splits_p =
-// round(K-tiles_p / L) (at least 1 — 2 with row sums, whose partials the reduce folds — and at
-// least 4 K-tiles per split), L chosen by the cost of the launch it gives:
+// round(K-tiles_p / L) (at least 1, at least 4 K-tiles per split; a one-split problem writes C
+// and its row sums from the GEMM kernel and has no reduce blocks), L chosen by the cost of the
+// launch it gives:
 //   rounds x (kKtUs x longest item + kItemUs) + kSlabUs x (items that write a slab)
 // with rounds = ceil(items / grid): the persistent grid runs whole rounds, so an L whose item
 // count just misses a multiple of the grid pays a whole round for the remainder.  kKtUs: one
@@ -986,8 +1025,6 @@ int group_check_one(const jmt_gemm_desc* d, const jmt_gemm_desc* d0, int i, int&
     bool any = false;
     for (int k = 0; k < batch0; ++k) any = any || d->dbias_tab[k] != nullptr;
     JMT_CHECK_ARG(any, "jmt_gemm_grouped: problem %d: every dbias_tab entry is null", i);
-    JMT_GRP_UNSUP(d->K >= 512 && d->splits != 1,
-                  "jmt_gemm_grouped: problem %d: row sums need at least 2 splits (K >= 512)", i);
   }
   if (d->splits > 1)
     JMT_GRP_UNSUP((d->K / 64) / norm_splits(d->K, d->splits) >= 2,
@@ -1009,13 +1046,12 @@ int group_plan(const jmt_gemm_desc* descs, int n, GroupPlan& pl) {
   }
   const int G = num_cus_persist();
   long tiles[GRP_MAXPROB];
-  int nkt[GRP_MAXPROB], smin[GRP_MAXPROB], maxkt = 4;
+  int nkt[GRP_MAXPROB], maxkt = 4;
   pl.rs = false;
   for (int i = 0; i < n; ++i) {
     const jmt_gemm_desc& d = descs[i];
     tiles[i] = (long)(d.M / 256) * (d.N / 256) * (d.batch0 < 1 ? 1 : d.batch0);
     nkt[i] = d.K / 64;
-    smin[i] = d.n_dbias > 0 ? 2 : 1;
     pl.rs = pl.rs || d.n_dbias > 0;
     if (nkt[i] > maxkt) maxkt = nkt[i];
   }
@@ -1023,7 +1059,7 @@ int group_plan(const jmt_gemm_desc* descs, int n, GroupPlan& pl) {
     if (descs[i].splits >= 1) return norm_splits(descs[i].K, descs[i].splits);   // forced
     int s = (nkt[i] + L / 2) / L;
     if (s > nkt[i] / 4) s = nkt[i] / 4;
-    if (s < smin[i]) s = smin[i];
+    if (s < 1) s = 1;
     return norm_splits(descs[i].K, s);
   };
   double best = 1e300;
@@ -1055,7 +1091,11 @@ int group_plan(const jmt_gemm_desc* descs, int n, GroupPlan& pl) {
   for (int i = 0; i < n; ++i) {
     const jmt_gemm_desc& d = descs[i];
     pl.rs_off[i] = off;
-    if (pl.rs) off += (int64_t)pl.splits[i] * (d.batch0 < 1 ? 1 : d.batch0) * d.M;
+    if (!pl.rs) continue;
+    // split partials [split][b0][M]; a one-split problem with a dbias table writes its sums to
+    // the table and keeps one 256-float tile for the stores of the items that own none
+    if (pl.splits[i] == 1 && d.n_dbias > 0) off += 256;
+    else off += (int64_t)pl.splits[i] * (d.batch0 < 1 ? 1 : d.batch0) * d.M;
   }
   JMT_CHECK_ARG(items < (1L << 30), "jmt_gemm_grouped: too many items");
   pl.items = (int)items;

@@ -142,12 +142,15 @@ __device__ __forceinline__ void persist_epilogue(const GemmParams& p, const PIte
                                                  bool nostore = false, bool part = false) {
   static_assert(C::TN % 2 == 0, "paired stores");
   T* cp;
+  const T* cinp;                // the beta * C operand (GemmParams::cin_ptr: C itself, or c_in)
   int64_t cbase;
   if (p.c_mode == 1) {
     cp = (T*)p.c_ptr[it.b0];
+    cinp = (const T*)p.cin_ptr[it.b0];
     cbase = (int64_t)it.b1 * p.sC1;
   } else {
     cp = (T*)p.c_ptr[0];
+    cinp = (const T*)p.cin_ptr[0];
     cbase = (int64_t)it.b0 * p.sC0 + (int64_t)it.b1 * p.sC1;
   }
   const int g = lane >> 4, rl = lane & 15;
@@ -198,7 +201,7 @@ __device__ __forceinline__ void persist_epilogue(const GemmParams& p, const PIte
 #pragma unroll
     for (int j = 0; j < C::TN; ++j) {
       const int n = it.n0 + wn * C::WTN + 16 * j + 4 * g;
-      if constexpr (ldc_) c[j] = *(const u32x2*)(cp + cbase + (int64_t)m * p.ldc + n);
+      if constexpr (ldc_) c[j] = *(const u32x2*)(cinp + cbase + (int64_t)m * p.ldcin + n);
       if constexpr (lda_) a[j] = *(const u32x2*)(auxp + cbase + (int64_t)m * p.ldaux + n);
     }
   };
@@ -1092,6 +1095,11 @@ __global__ __launch_bounds__(512) void gemm_pp_split_kernel(GemmParams p) {
 // dbias store theirs into their own partial area, which nobody reads), whether they go to a slab
 // or, for a problem with splits == 1, straight to C.  The beta * C loads of that direct form are
 // extra operations the deadline counts do not include: an undercount only waits for more.
+// A one-split problem with a dbias table finishes its row sums here as well: the item of column
+// panel 0 stores (dbias_acc ? d[m] : 0) + r into dbias_tab[b0][m] (rowsum_store's form in
+// gemm.hip; one writer per d[m], no atomics), its other items keep issuing their two stores into
+// the problem's partial area, so the store count per item stays uniform.  The owner's read of
+// d[m] is one more uncounted load, like the beta * C loads.
 struct GItem {
   int pi, m0, n0, b0, sp, kt0, len;
 };
@@ -1258,6 +1266,23 @@ __device__ __forceinline__ void ppg_run(const GroupParams& g, uint32_t lbase, co
     float* const sl = base + (int64_t)(cur.m0 + wm * C::WTM + rl) * stride + cur.n0 +
                       wn * C::WTN + 4 * gq;
     const float al = direct ? P.alpha : 1.f;               // slabs hold the raw partial sums
+    // SPL 2, a one-split problem with a dbias table: no reduce block folds its row sums, so the
+    // item of column panel 0 writes them to dbias_tab[b0][m] itself (one writer per d[m]; a NULL
+    // entry has none).  Its read of d[m] goes with the beta * C loads, ahead of the stores.
+    float* rs_own = nullptr;
+    float rs_old[2] = {0.f, 0.f};
+    if constexpr (SPL == 2) {
+      if (direct && P.d_off >= 0 && cur.n0 == 0) {
+        float* const d = (float*)const_cast<void*>(g.pool[P.d_off + cur.b0]);
+        if (d != nullptr) {
+          rs_own = d + cur.m0 + wm * C::WTM + 16 * wn + rl;
+          if (P.dbias_acc && lane < 16) {
+            rs_old[0] = rs_own[0];
+            rs_old[1] = rs_own[64];
+          }
+        }
+      }
+    }
     if (direct && P.beta != 0.f) {
       const float be = P.beta;
 #pragma unroll
@@ -1283,13 +1308,18 @@ __device__ __forceinline__ void ppg_run(const GroupParams& g, uint32_t lbase, co
       }
     }
     if constexpr (SPL == 2) {
-      float* const rs = g.ws + P.rs_off + ((int64_t)cur.sp * P.batch0 + cur.b0) * P.M + cur.m0 +
-                        wm * C::WTM + 16 * wn + rl;
+      // every item issues its two row-sum stores: the split partial [split][b0][M], the owned
+      // d[m] above, or — a one-split problem's other items — one 256-float tile of the problem's
+      // area that nobody reads
+      float* rs = g.ws + P.rs_off + wm * C::WTM + 16 * wn + rl;
+      if (!(direct && P.d_off >= 0)) rs += ((int64_t)cur.sp * P.batch0 + cur.b0) * P.M + cur.m0;
+      if (rs_own != nullptr) rs = rs_own;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         float v = rsum[h];
         v += __shfl_xor(v, 16);
         v += __shfl_xor(v, 32);
+        if (rs_own != nullptr) v = rs_old[h] + v;          // (dbias_acc ? d[m] : 0) + r
         if (lane < 16) rs[64 * h] = v;
         rsum[h] = 0.f;
       }

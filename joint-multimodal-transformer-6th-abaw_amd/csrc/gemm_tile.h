@@ -41,6 +41,11 @@ struct GemmParams {
   float* dbias_tab[MAXP];
   float* dbias_ws;
   int n_dbias, dbias_acc;
+  // the beta * C operand of the 16-bit epilogues: a table parallel to c_ptr (same c_mode, batch
+  // strides and dtype) with its own leading dimension.  jmt_gemm: c_ptr / ldc themselves;
+  // jmt_gemm_cin: another buffer (an accumulating dgrad that must leave its addend intact)
+  const void* cin_ptr[MAXP];
+  int64_t ldcin;
 };
 
 // PF: A-fragment prefetch distance in MFMA rows; PRIO: s_setprio(1) around each MFMA row;

@@ -59,6 +59,8 @@ _PROTOS = {
     "jmt_gemm_grouped": (c_int, [C.POINTER(GemmDesc), c_int, c_vp, C.c_size_t, c_vp]),
     "jmt_gemm_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(GemmDesc), c_int]),
     "jmt_gemm_grouped_plan": (c_int, [C.POINTER(GemmDesc), c_int, C.POINTER(c_int)]),
+    # jmt_gemm with the beta * C operand read from a table parallel to desc.c (c_in, n, ldcin)
+    "jmt_gemm_cin": (c_int, [C.POINTER(GemmDesc), c_vp, c_int, c_i64, c_vp]),
     "jmt_gemm_set_debug": (None, [c_int]),
     "jmt_gemm_trace_read": (c_int, [c_vp, c_int]),
     "jmt_l2norm_fwd": (c_int, [c_int, c_int, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_f,

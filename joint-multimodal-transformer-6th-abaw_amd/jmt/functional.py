@@ -274,9 +274,20 @@ def wgrad_group_ok() -> bool:
     return _grad_hook is None and ops.wgrad_group_enabled()
 
 
-def wgrad_scope():
-    """ops.wgrad_scope() where grouping is allowed, else a no-op context."""
-    return ops.wgrad_scope() if wgrad_group_ok() else contextlib.nullcontext()
+def wgrad_defer_ok(cd) -> bool:
+    """Whether a weight gradient of compute dtype `cd` whose operands stay intact may be held
+    until the end of the backward pass (ops: stage B, defer="late"): where grouping is allowed
+    and the grouped launch takes the operands (16-bit), unless JMT_WGRAD_DEFER=0 or the side
+    stream is on (its launches overlap the dgrad chain where they are issued)."""
+    return (wgrad_group_ok() and cd != torch.float32 and ops.wgrad_defer_mode() != "off" and
+            not streams.side_enabled())
+
+
+def wgrad_scope(cd=torch.float32):
+    """ops.wgrad_scope() where grouping is allowed (held for the end-of-backward flush where
+    wgrad_defer_ok(cd)), else a no-op context."""
+    return ops.wgrad_scope(defer=wgrad_defer_ok(cd)) if wgrad_group_ok() else \
+        contextlib.nullcontext()
 
 
 def _wgrad(G: Rows, n, xin, ld_in, kseg, W, r0, cd, b=None, defer: bool = False) -> bool:
@@ -310,7 +321,8 @@ def _wgrad(G: Rows, n, xin, ld_in, kseg, W, r0, cd, b=None, defer: bool = False)
              b_mode=1 if nseg > 1 else 0,
              c=[_ptr(gW, r0 * Kin)], ldc=Kin, batch0=nseg, sA=(0, 0), sB=(0, 0),
              sC=(kseg, 0), beta=1.0, dbias_tab=dbt, device=G.t.device,
-             done=done, keep=(G.t, gW, *xin, *(dbt or ())), defer=defer and wgrad_group_ok())
+             done=done, keep=(G.t, gW, *xin, *(dbt or ())),
+             defer=defer if wgrad_group_ok() else False)
     return dbt is not None
 
 

@@ -31,7 +31,7 @@ from torch.autograd import Function
 
 from . import ops, streams
 from .functional import (_dc, _grad_buffer, _grad_done, _ptr, attn_backward, attn_forward,
-                         attn_shared_ok, compute_dtype, weight_as, wgrad_scope)
+                         attn_shared_ok, compute_dtype, weight_as, wgrad_defer_ok, wgrad_scope)
 
 _enabled = {"on": os.environ.get("JMT_GROUPED", "1") != "0"}
 # the cross-attention backward's three stream-gradient GEMMs on branch streams: measured
@@ -75,24 +75,38 @@ def _gemm_fwd(a_ptrs: Sequence[int], lda: int, sA: int, rows: int, K: int, Ws, r
 
 def _gemm_dgrad(dy_ptr: int, ldy: int, sdy: int, rows: int, n: int, Ws, r0: int, c_ptr: int,
                 ldc: int, sC: int, c_dt: int, cd, dev, beta: float = 0.0, aux=None,
-                ldaux: int = 0):
-    """dX[g] (+)= dY[g] (rows x n) . W_g[r0:r0+n, :]  (masked by aux > 0: ReLU backward)."""
+                ldaux: int = 0, c_in=None):
+    """dX[g] (+)= dY[g] (rows x n) . W_g[r0:r0+n, :]  (masked by aux > 0: ReLU backward).
+    c_in (with beta != 0): dX[g] = beta * c_in[g] + ..., a (G, rows, Kin) buffer laid out like
+    dX that stays intact (jmt_gemm_cin).  Where the planner splits K — the reduce adds into C
+    itself — c_in is copied into dX first and the launch accumulates in place: the same bits."""
     Wc = [weight_as(W, cd) for W in Ws]
     Kin = Wc[0].shape[1]
+    cin_ptr = None
+    if c_in is not None:
+        assert beta != 0.0 and sC == rows * ldc and c_in.is_contiguous()
+        if ops.auto_splits(rows, Kin, n, len(Ws), _dc(cd)) > 1:
+            ops.copy2d(c_in.data_ptr(), ops.dt(c_in), c_ptr, c_dt, len(Ws) * rows, Kin, ldc, 1,
+                       ldc, 1)
+        else:
+            cin_ptr = [c_in.data_ptr()]
     ops.gemm(M=rows, N=Kin, K=n, ab_dtype=_dc(cd), c_dtype=c_dt,
              a=[dy_ptr], lda=ldy, a_kmajor=True, sA=(sdy, 0),
              b=[_ptr(w, r0 * Kin) for w in Wc], ldb=Kin, b_kmajor=False, b_mode=1,
              c=[c_ptr], ldc=ldc, sC=(sC, 0), batch0=len(Ws), beta=beta,
-             aux=aux, ldaux=ldaux, device=dev)
+             aux=aux, ldaux=ldaux, device=dev, c_in=cin_ptr, ldcin=ldc)
 
 
 def _gemm_wgrad(dy_ptrs: Sequence[int], ldy: int, sdy: int, x_ptrs: Sequence[int], ldx: int,
-                sx: int, rows: int, n: int, Ws, r0: int, cd, dev, bs=None) -> bool:
+                sx: int, rows: int, n: int, Ws, r0: int, cd, dev, bs=None, reads=None) -> bool:
     """W_g.grad[r0:r0+n] += dY[g]^T X[g]  (fp32, split-K over the rows).  dY / X are strided
     ([base], stride) or per-group pointer tables.  The Ws of one launch must be distinct
     parameters (their gradient regions are written concurrently).  With `bs` (distinct bias
     parameters), also b_g.grad[r0:r0+n] += the column sums of dY[g], taken inside the same GEMM
-    (functional.fused_bgrad_ok); returns True when the bias gradients were written."""
+    (functional.fused_bgrad_ok); returns True when the bias gradients were written.
+    reads: the tensors dY and X live in, when nothing writes them again before the end of the
+    backward pass — the launch may then be held for the end-of-backward group (ops: stage B)
+    where functional.wgrad_defer_ok(cd)."""
     from .functional import fused_bgrad_ok
     grads = []
     for W in Ws:
@@ -119,7 +133,9 @@ def _gemm_wgrad(dy_ptrs: Sequence[int], ldy: int, sdy: int, x_ptrs: Sequence[int
              b=list(x_ptrs), ldb=ldx, b_kmajor=False, b_mode=1 if tb else 0,
              sB=(0 if tb else sx, 0),
              c=[_ptr(g, r0 * Kin) for g in grads], ldc=Kin, c_mode=1, batch0=len(Ws),
-             beta=1.0, dbias_tab=dbt, device=dev, done=done, keep=(*grads, *(dbt or ())))
+             beta=1.0, dbias_tab=dbt, device=dev, done=done,
+             keep=(*grads, *(dbt or ()), *(reads or ())),
+             defer="late" if reads is not None and wgrad_defer_ok(cd) else False)
     return dbt is not None
 
 
@@ -135,12 +151,13 @@ _merge_wgrads = {"on": os.environ.get("JMT_WGRAD_MERGE", "1") != "0"}
 
 
 def _gemm_wgrad_kcat(dy_segs, ldy: int, x_segs, ldx: int, rows: int, n: int, Ws, r0: int, cd,
-                     dev, bs=None) -> bool:
+                     dev, bs=None, reads=None) -> bool:
     """W_g.grad[r0:r0+n] += sum_s dY[g][s]^T X[g][s]: each weight's uses as the K-segments of ONE
     batch entry (jmt_gemm operand mode 3, K = len(segments) x rows), so the two uses of a module
     are one (256 x 256 tile, K = 2 rows) item set of the split-K ping-pong kernel instead of two
     12-tile launches on the 128 x 128 split plan.  With `bs`, b_g.grad += the column sums of all
-    of dY[g]'s segments (the row sums of A over the whole K).  Returns as _gemm_wgrad."""
+    of dY[g]'s segments (the row sums of A over the whole K).  Returns and `reads` as
+    _gemm_wgrad."""
     from .functional import fused_bgrad_ok
     nseg = len(dy_segs[0])
     assert all(len(d) == nseg for d in dy_segs) and all(len(x) == nseg for x in x_segs)
@@ -166,7 +183,9 @@ def _gemm_wgrad_kcat(dy_segs, ldy: int, x_segs, ldx: int, rows: int, n: int, Ws,
              a=[p for d in dy_segs for p in d], lda=ldy, a_kmajor=False, a_mode=3, a_kseg=rows,
              b=[p for x in x_segs for p in x], ldb=ldx, b_kmajor=False, b_mode=3, b_kseg=rows,
              c=[_ptr(g, r0 * Kin) for g in grads], ldc=Kin, c_mode=1, batch0=len(Ws),
-             beta=1.0, dbias_tab=dbt, device=dev, done=done, keep=(*grads, *(dbt or ())))
+             beta=1.0, dbias_tab=dbt, device=dev, done=done,
+             keep=(*grads, *(dbt or ()), *(reads or ())),
+             defer="late" if reads is not None and wgrad_defer_ok(cd) else False)
     return dbt is not None
 
 
@@ -524,6 +543,15 @@ class EncoderGroupFn(Function):
         # 2 G entries of 512 x 512 over the B T rows (24 tiles at G = 3: the split-K ping-pong
         # kernel) instead of two 12-tile launches on the 128 x 128 split plan
         merged = _merge_wgrads["on"] and hid == E and 2 * G <= 8 and cd != torch.float32
+        # stage B (ops: the end-of-backward group): the weight gradients below are queued, so
+        # nothing may write their operands again before the backward pass ends —
+        #   W2 (+ W1 merged)  dS, F1 (+ dF1, H1)   dH1 goes to a fresh buffer (c_in = dS) and dO
+        #                                          takes that buffer, dead after LN1's backward
+        #   W1                dF1, H1              not written again
+        #   out_proj          dS1, O               dX goes to a fresh buffer (c_in = dS1)
+        #   in_proj           dQKV, X              not written again (X: the saved input)
+        # F1, H1, O and X are saved forward buffers that the backward only reads.
+        late = wgrad_defer_ok(cd)
         if merged:
             ws = [p[6] for p in P] + [p[4] for p in P]
             # b2 already summed (by LN2's backward): its entries stay NULL and W1's bias
@@ -533,7 +561,7 @@ class EncoderGroupFn(Function):
                                 [dF1[g].data_ptr() for g in range(G)], E, 0,
                                 [F1[g].data_ptr() for g in range(G)] +
                                 [H1[g].data_ptr() for g in range(G)], E, 0, R, E, ws, 0, cd, dev,
-                                bs=bsw)
+                                bs=bsw, reads=(dS, dF1, F1, H1) if late else None)
             if not fused:
                 if not b2_done:
                     _bias_grad_grouped(dS.data_ptr(), G, E, R * E, R, E, [p[7] for p in P], 0,
@@ -544,16 +572,20 @@ class EncoderGroupFn(Function):
         else:
             b2_done = _gemm_wgrad([dS.data_ptr()], E, R * E, [F1.data_ptr()], hid, R * hid, R, E,
                                   [p[6] for p in P], 0, cd, dev,
-                                  bs=None if b2_done else [p[7] for p in P]) or b2_done
+                                  bs=None if b2_done else [p[7] for p in P],
+                                  reads=(dS, F1) if late else None) or b2_done
         if not b2_done:
             _bias_grad_grouped(dS.data_ptr(), G, E, R * E, R, E, [p[7] for p in P], 0, cd, dev)
-        # dH1 = dS2 + dF1 . W1  (in place on dS: beta = 1)
-        _gemm_dgrad(dF1.data_ptr(), hid, R * hid, R, hid, [p[4] for p in P], 0, dS.data_ptr(),
-                    E, R * E, cdt, cd, dev, beta=1.0)
+        # dH1 = dS2 + dF1 . W1  (in place on dS: beta = 1; stage B: into a fresh buffer, dS is
+        # the queued W2 weight gradient's operand)
+        dH1 = torch.empty_like(dS) if late else dS
+        _gemm_dgrad(dF1.data_ptr(), hid, R * hid, R, hid, [p[4] for p in P], 0, dH1.data_ptr(),
+                    E, R * E, cdt, cd, dev, beta=1.0, c_in=dS if late else None)
 
         def w1_grads():         # side stream: dF1 and H1 are not written again
             if not _gemm_wgrad([dF1.data_ptr()], hid, R * hid, [H1.data_ptr()], E, R * E, R,
-                               hid, [p[4] for p in P], 0, cd, dev, bs=[p[5] for p in P]):
+                               hid, [p[4] for p in P], 0, cd, dev, bs=[p[5] for p in P],
+                               reads=(dF1, H1) if late else None):
                 _bias_grad_grouped(dF1.data_ptr(), G, hid, R * hid, R, hid, [p[5] for p in P], 0,
                                    cd, dev)
 
@@ -561,17 +593,18 @@ class EncoderGroupFn(Function):
             streams.run_side(w1_grads, reads=(dF1, H1))
         # LN1: dS1 = d(X + A1)
         dS1 = torch.empty_like(dS)
-        bo_done = ln_bwd(X, A1, dS, st1, [p[8] for p in P], [p[9] for p in P], dS1,
+        bo_done = ln_bwd(X, A1, dH1, st1, [p[8] for p in P], [p[9] for p in P], dS1,
                          bias=[p[3] for p in P])
         # out_proj
-        dO = dS     # reuse: dS is dead
+        dO = dH1    # reuse: dH1 is dead
         _gemm_dgrad(dS1.data_ptr(), E, R * E, R, E, [p[2] for p in P], 0, dO.data_ptr(), E,
                     R * E, cdt, cd, dev)
 
         def out_proj_grads():   # side stream, under the attention backward
             done = _gemm_wgrad([dS1.data_ptr()], E, R * E, o_ptrs, E,
                                R * E if len(o_ptrs) == 1 else 0, R, E, [p[2] for p in P], 0, cd,
-                               dev, bs=None if bo_done else [p[3] for p in P])
+                               dev, bs=None if bo_done else [p[3] for p in P],
+                               reads=(dS1,) + o_reads if late else None)
             if not (bo_done or done):
                 _bias_grad_grouped(dS1.data_ptr(), G, E, R * E, R, E, [p[3] for p in P], 0, cd,
                                    dev)
@@ -585,20 +618,24 @@ class EncoderGroupFn(Function):
         else:
             dsf = dQKV.view(G * B, T, 3 * E).permute(1, 0, 2)
             attn_backward(asaved, dO.view(G * B, T, E).permute(1, 0, 2), dsf, dsf, dsf)
-        # in_proj: dX = dS1 + dQKV . W_in  (in place on dS1, once the side stream has read it)
+        # in_proj: dX = dS1 + dQKV . W_in  (in place on dS1, once the side stream has read it;
+        # stage B: into a fresh buffer, dS1 is the queued out_proj weight gradient's operand —
+        # the returned dX is accumulated into again downstream, StackJointFn)
         streams.wait_side()
+        dX = torch.empty_like(dS1) if late else dS1
         _gemm_dgrad(dQKV.data_ptr(), 3 * E, R * 3 * E, R, 3 * E, [p[0] for p in P], 0,
-                    dS1.data_ptr(), E, R * E, cdt, cd, dev, beta=1.0)
+                    dX.data_ptr(), E, R * E, cdt, cd, dev, beta=1.0, c_in=dS1 if late else None)
 
         def in_proj_grads():    # side stream: dQKV and X are not written again
             if not _gemm_wgrad([dQKV.data_ptr()], 3 * E, R * 3 * E, [X.data_ptr()], E, R * E, R,
-                               3 * E, [p[0] for p in P], 0, cd, dev, bs=[p[1] for p in P]):
+                               3 * E, [p[0] for p in P], 0, cd, dev, bs=[p[1] for p in P],
+                               reads=(dQKV, X) if late else None):
                 _bias_grad_grouped(dQKV.data_ptr(), G, 3 * E, R * 3 * E, R, 3 * E,
                                    [p[1] for p in P], 0, cd, dev)
 
         streams.run_side(in_proj_grads, reads=(dQKV, X))
         ctx.state = None
-        return (dS1, None) + (None,) * len(params)
+        return (dX, None) + (None,) * len(params)
 
 
 def encoder_group(X, layers, num_heads: int, batch_axis: bool = False):
@@ -698,6 +735,13 @@ class CrossAttention6Fn(Function):
         dev = Y.device
         cdt = _dc(cd)
         dO6 = _contig(dO6, cd)
+        # stage B (ops: the end-of-backward group): the weight gradients are queued with their
+        # operand tensors.  dO6 is this node's incoming gradient (ConcatLinearFn's fresh dX, or
+        # StackTokensFn's on the SELF_ATTEN head path: autograd has summed into it before this
+        # node runs and nobody holds it afterwards), O and Y are saved forward buffers, and dQKV
+        # is only read after the attention backward has written it.
+        late = wgrad_defer_ok(cd)
+        rd_o = (dO6, O) if late else None
         # launches of the batched wgrads: each launch holds distinct modules
         halves, seen = [[]], [set()]
         for i, (m, _, _) in enumerate(pairs):
@@ -735,7 +779,7 @@ class CrossAttention6Fn(Function):
                                      for i, j in zip(h0, h1)], E,
                                     [[O[i * B].data_ptr(), O[j * B].data_ptr()]
                                      for i, j in zip(h0, h1)], E, R, E, [M[m][2] for m in ms],
-                                    0, cd, dev, bs=[M[m][3] for m in ms]):
+                                    0, cd, dev, bs=[M[m][3] for m in ms], reads=rd_o):
                     return
                 for m, i, j in zip(ms, h0, h1):
                     _bias_grad(dO6[i], E, R, E, M[m][3], 0)
@@ -746,7 +790,7 @@ class CrossAttention6Fn(Function):
                 if not _gemm_wgrad([_ptr(dO6, i * R * E) for i in h], E, 0,
                                    [O[i * B].data_ptr() for i in h], E, 0, R, E,
                                    [M[pairs[i][0]][2] for i in h], 0, cd, dev,
-                                   bs=[M[pairs[i][0]][3] for i in h]):
+                                   bs=[M[pairs[i][0]][3] for i in h], reads=rd_o):
                     rest.append(h)
             for h in rest:
                 if _consecutive(h):
@@ -759,6 +803,7 @@ class CrossAttention6Fn(Function):
         streams.run_side(out_proj_grads, reads=(dO6, O))
         # attention core -> packed dQKV (NP, B, T, 3E)
         dQKV = torch.empty(NP, B, T, 3 * E, dtype=cd, device=dev)
+        rd_i = (dQKV, Y) if late else None
         dsf = dQKV.view(NP * B, T, 3 * E).permute(1, 0, 2)
         attn_backward(asaved, dO.view(NP * B, T, E).permute(1, 0, 2), dsf, dsf, dsf,
                       qshare=(B, qtab) if qtab is not None else None, merge_dq=merge)
@@ -773,22 +818,22 @@ class CrossAttention6Fn(Function):
                                    for i, j in zip(h0, h1)]
                 # the query-row and key / value-row launches sit next to each other: one
                 # grouped launch (their rows of W.grad / b.grad are disjoint)
-                with wgrad_scope():
+                with wgrad_scope(cd):
                     if merge:
                         # the merged dQ against the query stream: a plain problem over K = B T
                         fq = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E) for i in h0], 3 * E, 0,
                                          [Y[pairs[i][1]].data_ptr() for i in h0], E, 0, R, E, ws,
-                                         0, cd, dev, bs=bs)
+                                         0, cd, dev, bs=bs, reads=rd_i)
                     else:
                         fq = _gemm_wgrad_kcat(seg(0), 3 * E,
                                               [[Y[pairs[i][1]].data_ptr(),
                                                 Y[pairs[j][1]].data_ptr()]
                                                for i, j in zip(h0, h1)], E, R, E, ws, 0, cd, dev,
-                                              bs=bs)
+                                              bs=bs, reads=rd_i)
                     fkv = _gemm_wgrad_kcat(seg(E), 3 * E,
                                            [[Y[pairs[i][2]].data_ptr(), Y[pairs[j][2]].data_ptr()]
                                             for i, j in zip(h0, h1)], E, R, 2 * E, ws, E, cd, dev,
-                                           bs=bs if fq else None)
+                                           bs=bs if fq else None, reads=rd_i)
                 if not (fq and fkv):
                     assert not fq, "query-row bias sums fused without the key / value rows"
                     for m, i, j in zip(ms, h0, h1):
@@ -805,15 +850,15 @@ class CrossAttention6Fn(Function):
                 if merge:
                     # query rows from the pairs that hold a (merged) dQ only
                     hq = [i for i in h if qtab[i] == i]
-                    with wgrad_scope():
+                    with wgrad_scope(cd):
                         fq = not hq or _gemm_wgrad(
                             [_ptr(dQKV, i * R * 3 * E) for i in hq], 3 * E, 0,
                             [Y[pairs[i][1]].data_ptr() for i in hq], E, 0, R, E,
                             [M[pairs[i][0]][0] for i in hq], 0, cd, dev,
-                            bs=[M[pairs[i][0]][1] for i in hq])
+                            bs=[M[pairs[i][0]][1] for i in hq], reads=rd_i)
                         fkv = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E + E) for i in h], 3 * E, 0,
                                           [Y[pairs[i][2]].data_ptr() for i in h], E, 0, R, 2 * E,
-                                          ws, E, cd, dev, bs=bs if fq else None)
+                                          ws, E, cd, dev, bs=bs if fq else None, reads=rd_i)
                     if not (fq and fkv):
                         assert not (fq and hq), "query-row bias sums fused without the others"
                         for i in h:
@@ -821,13 +866,13 @@ class CrossAttention6Fn(Function):
                             _bias_grad(dQKV[i].view(R, 3 * E)[:, c0:], 3 * E, R, 3 * E - c0,
                                        M[pairs[i][0]][1], c0)
                     continue
-                with wgrad_scope():
+                with wgrad_scope(cd):
                     fq = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E) for i in h], 3 * E, 0,
                                      [Y[pairs[i][1]].data_ptr() for i in h], E, 0, R, E, ws, 0,
-                                     cd, dev, bs=bs)
+                                     cd, dev, bs=bs, reads=rd_i)
                     fkv = _gemm_wgrad([_ptr(dQKV, i * R * 3 * E + E) for i in h], 3 * E, 0,
                                       [Y[pairs[i][2]].data_ptr() for i in h], E, 0, R, 2 * E, ws,
-                                      E, cd, dev, bs=bs if fq else None)
+                                      E, cd, dev, bs=bs if fq else None, reads=rd_i)
                 if not (fq and fkv):
                     assert not fq, "query-row bias sums fused without the key / value rows"
                     rest.append(h)
@@ -934,19 +979,25 @@ class ConcatLinearFn(Function):
             gW = _grad_buffer(W)
             gb = _grad_buffer(b)
             fuse = gW is not None and gb is not None and N > 1 and fused_bgrad_ok(cd)
+            def done():
+                _grad_done(W)
+                if fuse:
+                    _grad_done(b)
+
             if gW is not None:
-                # the S K-segments share dY: segment 0 also takes its row sums (the bias grad)
+                # the S K-segments share dY: segment 0 also takes its row sums (the bias grad).
+                # Stage B (ops: the end-of-backward group): dy is this node's incoming gradient
+                # (autograd has summed the regressors' into it before this node runs) and X its
+                # saved input; neither is written again
                 ops.gemm(M=N, N=E, K=R, ab_dtype=_dc(cd), c_dtype=ops.F32,
                          a=[dy.data_ptr()], lda=N, a_kmajor=False, sA=(0, 0),
                          b=[X.data_ptr()], ldb=E, b_kmajor=False, sB=(R * E, 0),
                          c=[gW.data_ptr()], ldc=S * E, sC=(E, 0), batch0=S, beta=1.0,
-                         dbias_tab=[gb] + [None] * (S - 1) if fuse else None, device=dev)
-                _grad_done(W)
-            if b is not None:
-                if fuse:
-                    _grad_done(b)
-                else:
-                    _bias_grad(dy, N, R, N, b, 0)
+                         dbias_tab=[gb] + [None] * (S - 1) if fuse else None, device=dev,
+                         done=done, keep=(dy, X, gW, gb),
+                         defer="late" if wgrad_defer_ok(cd) else False)
+            if b is not None and not fuse:
+                _bias_grad(dy, N, R, N, b, 0)
 
         streams.run_side(param_grads, reads=(dy, X))
         return dX, None, None

@@ -62,13 +62,17 @@ def gemm(*, M: int, N: int, K: int, ab_dtype: int, c_dtype: int,
          alpha: float = 1.0, beta: float = 0.0, bias: Optional[torch.Tensor] = None,
          bias_mode: int = 1, relu: bool = False, aux: Optional[torch.Tensor] = None,
          ldaux: int = 0, splits: Optional[int] = None, bias_tab=None, dbias_tab=None,
-         dbias_acc: bool = True, device=None, done=None, keep=(), defer: bool = False) -> None:
+         dbias_acc: bool = True, device=None, done=None, keep=(), defer: bool = False,
+         c_in: Optional[Sequence[int]] = None, ldcin: int = 0) -> None:
     """dbias_tab: per-b0 fp32 outputs (None: skip that entry) that receive (dbias_acc: += ) the
     row sums of A — a weight-gradient GEMM's bias gradient (jmt_gemm_desc ABI 4).
+    c_in / ldcin: the epilogue's beta * C operand comes from this table (parallel to `c`, its own
+    leading dimension) and C is only written (jmt_gemm_cin: 16-bit C, no split-K).
     done: called once the launch is enqueued (a weight gradient's completion report).  A launch
-    with `done` may be held in the weight-gradient queue (wgrad_scope, or with defer=True until
-    the end of the running backward pass) and flushed with its neighbours as one
-    jmt_gemm_grouped launch; `keep` are the tensors its operands live in."""
+    with `done` may be held in the weight-gradient queue (wgrad_scope, or with defer=True /
+    defer="late" — stage A / stage B below — until the end of the running backward pass) and
+    flushed with its neighbours as one jmt_gemm_grouped launch; `keep` are the tensors its
+    operands live in."""
     d = GemmDesc()
     d.ab_dtype, d.c_dtype = ab_dtype, c_dtype
     d.aux_dtype = dt(aux) if aux is not None else c_dtype
@@ -129,7 +133,12 @@ def gemm(*, M: int, N: int, K: int, ab_dtype: int, c_dtype: int,
                 ws = workspace(nbytes, device)
             d.workspace = ws.data_ptr()
             d.ws_bytes = nbytes
-        launch = lambda: _lib.check(_lib.load().jmt_gemm(C.byref(d), stream()), "jmt_gemm")
+        if c_in is not None:
+            tab = (C.c_void_p * len(c_in))(*c_in)
+            launch = lambda: _lib.check(_lib.load().jmt_gemm_cin(
+                C.byref(d), tab, len(c_in), ldcin or ldc, stream()), "jmt_gemm_cin")
+        else:
+            launch = lambda: _lib.check(_lib.load().jmt_gemm(C.byref(d), stream()), "jmt_gemm")
         if _launch_hook is not None:
             _launch_hook(info, launch)
         else:
@@ -148,35 +157,49 @@ def gemm(*, M: int, N: int, K: int, ab_dtype: int, c_dtype: int,
 # ------------------------------------------------------------------ grouped weight gradients
 # The step's weight gradients are few 256 x 256 tiles over a long K each: launched one by one,
 # every launch spreads its tiles over a full grid of split-K items and pays a slab set and a
-# reduce launch of its own.  Launches that sit next to each other are queued instead and flushed
-# as ONE jmt_gemm_grouped launch (+ one reduce).  JMT_WGRAD_GROUP=0: every launch as before.
+# reduce launch of its own.  Launches are queued instead and flushed as jmt_gemm_grouped launches
+# (+ one reduce each).  JMT_WGRAD_GROUP=0: every launch as before.
+#
+# Who is queued (rounds 8 and 11):
+#   stage A  launches that already sit next to each other: the calls inside a wgrad_scope(),
+#            and the backward's last three (defer=True), flushed by an end-of-backward callback;
+#   stage B  every weight gradient whose operands are left intact until the end of the backward
+#            (defer="late"): held with the stage-A entries and flushed with them as ONE group.
+# JMT_WGRAD_DEFER=0 switches stage B off (stage A as before); JMT_WGRAD_DEFER=single holds the
+# stage-B entries to the end of the backward but launches what stage A launches, unit by unit —
+# the same launches as JMT_WGRAD_DEFER=0, only later, so an operand overwritten before the flush
+# shows as a bitwise difference.
 _wgrad_group = {"on": os.environ.get("JMT_WGRAD_GROUP", "1") != "0"}
+_wgrad_defer = {"mode": {"0": "off", "single": "single"}.get(
+    os.environ.get("JMT_WGRAD_DEFER", "1"), "on")}
 
 
 def wgrad_group_enabled() -> bool:
     return _wgrad_group["on"]
 
 
+def wgrad_defer_mode() -> str:
+    """'off', 'single' or 'on' (JMT_WGRAD_DEFER); 'off' without grouping."""
+    return _wgrad_defer["mode"] if _wgrad_group["on"] else "off"
+
+
 class _WgradEntry:
     __slots__ = ("d", "info", "single", "done", "keep", "device", "stream")
 
-    def __init__(self, d, info, single, done, keep, device):
+    def __init__(self, d, info, single, done, keep, device, stream=None):
         self.d, self.info, self.single, self.done = d, info, single, done
         self.keep, self.device = keep, device
-        self.stream = torch.cuda.current_stream()
+        self.stream = stream if stream is not None else torch.cuda.current_stream()
 
 
-_wq = {"depth": 0, "scoped": [], "deferred": [], "task": None}
+# deferred: the units held for the end-of-backward callback, in program order.  A unit is
+# (kind, entries): "tail" a stage-A deferred entry, "scope" the entries of one wgrad_scope,
+# "late" a stage-B entry.
+_wq = {"depth": 0, "scoped": [], "deferred": [], "task": None, "scope_defer": False}
 
 
-def _wgrad_enqueue(e: "_WgradEntry", defer: bool) -> bool:
-    if not _wgrad_group["on"]:
-        return False
-    if _wq["depth"] > 0:
-        _wq["scoped"].append(e)
-        return True
-    if not defer:
-        return False
+def _wgrad_hold(kind: str, ents) -> bool:
+    """Queue a unit for the end-of-backward flush; False outside a backward pass."""
     task = torch._C._current_graph_task_id()
     if task < 0:                        # outside a backward pass: nothing would flush it
         return False
@@ -186,19 +209,54 @@ def _wgrad_enqueue(e: "_WgradEntry", defer: bool) -> bool:
 
         def _cb():
             _wq["task"] = None
-            ents, _wq["deferred"] = _wq["deferred"], []
-            wgrad_flush(ents)
+            units, _wq["deferred"] = _wq["deferred"], []
+            _wgrad_flush_units(units)
 
         torch.autograd.Variable._execution_engine.queue_callback(_cb)
-    _wq["deferred"].append(e)
+    _wq["deferred"].append((kind, list(ents)))
     return True
+
+
+def _wgrad_flush_units(units) -> None:
+    if wgrad_defer_mode() == "on":      # stage B: everything as one flush
+        wgrad_flush([e for _, ents in units for e in ents])
+        return
+    # stage A's launches: every scope as its own flush, every stage-B entry alone, the stage-A
+    # tail together and last (where it already ran)
+    tail = []
+    for kind, ents in units:
+        if kind == "tail":
+            tail += ents
+        else:
+            wgrad_flush(ents)
+    wgrad_flush(tail)
+
+
+def _wgrad_enqueue(e: "_WgradEntry", defer) -> bool:
+    if not _wgrad_group["on"]:
+        return False
+    if _wq["depth"] > 0:
+        _wq["scoped"].append(e)
+        return True
+    if defer == "late":
+        return wgrad_defer_mode() != "off" and _wgrad_hold("late", [e])
+    if not defer:
+        return False
+    return _wgrad_hold("tail", [e])
 
 
 class wgrad_scope:
     """Weight-gradient launches issued inside (ops.gemm with `done`) are flushed together at the
-    exit, on the stream current there: for launches that already sit next to each other."""
+    exit, on the stream current there: for launches that already sit next to each other.
+    defer: with stage B on, the entries are held for the end-of-backward flush instead (their
+    operands must stay intact until then)."""
+
+    def __init__(self, defer: bool = False):
+        self.defer = bool(defer)
 
     def __enter__(self):
+        if _wq["depth"] == 0:
+            _wq["scope_defer"] = self.defer
         _wq["depth"] += 1
         return self
 
@@ -207,22 +265,38 @@ class wgrad_scope:
         if _wq["depth"] == 0:
             ents, _wq["scoped"] = _wq["scoped"], []
             if et is None:
-                wgrad_flush(ents)
+                if not (_wq["scope_defer"] and wgrad_defer_mode() != "off" and
+                        _wgrad_hold("scope", ents)):
+                    wgrad_flush(ents)
         return False
 
 
-def wgrad_flush(entries) -> None:
-    """Launch the queued weight gradients on the current stream: those the grouped form takes
-    (jmt_gemm_grouped_plan says so per entry) as grouped launches of up to 16 problems, the rest
-    (the 128-row regressor gradient, fp32 compute, ...) through jmt_gemm as before; then report
-    every entry done."""
-    if not entries:
-        return
+def _out_ranges(d):
+    """The byte ranges [lo, hi) a queued problem writes: C per batch entry and the dbias rows."""
+    nb = max(int(d.batch0), 1)
+    span = ((d.M - 1) * d.ldc + d.N) * 4
+    out = []
+    for b in range(nb):
+        lo = d.c[b] if d.c_mode == 1 else d.c[0] + b * d.sC0 * 4
+        out.append((lo, lo + span))
+    for b in range(min(int(d.n_dbias), nb)):
+        if d.dbias_tab[b]:
+            out.append((d.dbias_tab[b], d.dbias_tab[b] + d.M * 4))
+    return out
+
+
+def _overlaps(ra, rb) -> bool:
+    return any(a0 < b1 and b0 < a1 for a0, a1 in ra for b0, b1 in rb)
+
+
+def wgrad_partition(entries):
+    """(groups, rest): the entries jmt_gemm_grouped takes (jmt_gemm_grouped_plan says so per
+    entry) as groups of up to 16 problems of one dtype / layout / device within the pointer pool,
+    the others in `rest`.  Two problems of one launch read-modify-write their outputs
+    concurrently, so an entry whose C or dbias ranges overlap an earlier entry's goes into a
+    later launch than that entry's (the two halves of a module outside the K-concat path,
+    beta = 1 onto the same rows).  A pure host function."""
     lib = _lib.load()
-    cur = torch.cuda.current_stream()
-    for st in {e.stream for e in entries}:
-        if st != cur:                   # operands written on a branch stream
-            cur.wait_stream(st)
     groups, rest = [], []
     for e in entries:
         e.d.splits = 0
@@ -230,17 +304,41 @@ def wgrad_flush(entries) -> None:
             rest.append(e)
             continue
         key = (e.d.ab_dtype, e.d.a_kmajor, e.d.b_kmajor, e.device)
-        for g in groups:
+        rng = _out_ranges(e.d)
+        first = 0                       # the first group after every overlapping earlier entry
+        for gi, g in enumerate(groups):
+            if any(_overlaps(rng, r) for r in g[2]):
+                first = gi + 1
+        for g in groups[first:]:
             if g[0] == key and len(g[1]) < 16 and \
                     sum(x.d.n_a + x.d.n_b + x.d.n_c + x.d.n_dbias for x in g[1] + [e]) <= 216:
                 g[1].append(e)
+                g[2].append(rng)
                 break
         else:
-            groups.append((key, [e]))
-    for _, ents in groups:
+            groups.append((key, [e], [rng]))
+    out = []
+    for _, ents, _ in groups:
         if len(ents) == 1:
             rest.append(ents[0])
-            continue
+        else:
+            out.append(ents)
+    return out, rest
+
+
+def wgrad_flush(entries) -> None:
+    """Launch the queued weight gradients on the current stream: those the grouped form takes as
+    grouped launches (wgrad_partition), the rest (the 128-row regressor gradient, fp32 compute,
+    ...) through jmt_gemm as before; then report every entry done."""
+    if not entries:
+        return
+    lib = _lib.load()
+    cur = torch.cuda.current_stream()
+    for st in {e.stream for e in entries}:
+        if st != cur:                   # operands written on a branch stream
+            cur.wait_stream(st)
+    groups, rest = wgrad_partition(entries)
+    for ents in groups:
         n = len(ents)
         arr = (GemmDesc * n)(*[e.d for e in ents])
         nbytes = lib.jmt_gemm_grouped_workspace_bytes(arr, n)

@@ -107,6 +107,11 @@ def set_side_enabled(on: bool) -> None:
     _enabled["side"] = bool(on)
 
 
+def side_enabled() -> bool:
+    """Whether run_side moves weight-gradient launches to the side stream."""
+    return _enabled["on"] and _enabled["side"]
+
+
 def side_streams() -> List[torch.cuda.Stream]:
     """The side streams created so far (jmt.dist.GradBucketer gates its all-reduces on them)."""
     return list(_side.values())
