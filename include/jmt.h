@@ -299,6 +299,27 @@ int jmt_attn_dkdv_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* p
                      int64_t sdv_n, void* dq, int64_t sdq_l, int64_t sdq_n, int spp,
                      const int* qtab, int npair, int merge_dq, void* stream);
 
+/* The ranges of the attention kernels (round 12; added to ABI 7, nothing else changes): the
+ * size and row-stride conditions the entry points above validate with, asked without a launch.
+ * No pointer, no GPU call, 0 or 1.  Strides in elements of the 16-bit dtype; dtype / head dim are
+ * jmt_attn_supported's question, pointer alignment and strides % 8 the caller's contract.
+ *   jmt_attn_fwd_rows_ok: jmt_attn_fwd takes the whole-row kernel (128-row items), so
+ *     jmt_attn_fwd_sq accepts the call: Lq > 64, Lk rows of K and of V below 2 GiB
+ *     (Lk * s*_l * 2 B < 2^31), fewer than 2^31 items, and the forward-rows switch on
+ *     (JMT_ATTN_FWD_ROWS, read once).
+ *   jmt_attn_bwd_pds_ok: jmt_attn_bwd with dq == NULL accepts them: ldp a multiple of 32 >= Lk,
+ *     (Lq + 128) * ldp 16-bit values below 1 GiB, Lk rows of K and of V below 2 GiB, fewer than
+ *     2^31 128-row items.
+ *   jmt_attn_dkdv_ok: jmt_attn_dkdv accepts them, has_dq != 0 with dq: ldp >= 128 ceil(Lk / 128);
+ *     dK / dV row strides >= 512 H with 128 rows below 2 GiB; Lq rows of dO, Q and P below 2 GiB;
+ *     fewer than 2^31 items of the tile jmt_attn_dkdv_plan picks; with dq also its row stride in
+ *     the dK / dV range, Lk rows of K below 2 GiB and ldp % 32 == 0 (sk_l, sdq_l ignored
+ *     otherwise). */
+int jmt_attn_fwd_rows_ok(int N, int H, int Lq, int Lk, int64_t sk_l, int64_t sv_l);
+int jmt_attn_bwd_pds_ok(int N, int H, int Lq, int Lk, int64_t ldp, int64_t sk_l, int64_t sv_l);
+int jmt_attn_dkdv_ok(int N, int H, int Lq, int Lk, int64_t ldp, int64_t sgo_l, int64_t sq_l,
+                     int64_t sk_l, int64_t sdk_l, int64_t sdv_l, int64_t sdq_l, int has_dq);
+
 /* Fused attention over short sequences, the whole backward in one kernel (Lq, Lk <= 32, 16-bit,
  * dh = 512; the batch-axis self-attention of mm_transformers.py:119-146 at B = 32 and every
  * attention of the T = 16 real-data configuration): same element addressing as jmt_attn_*,

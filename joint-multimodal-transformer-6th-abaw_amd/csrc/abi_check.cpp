@@ -30,6 +30,23 @@ static void expect_err(const char* what, int rc) {
   }
 }
 
+static void expect_eq(const char* what, int got, int want) {
+  if (got != want) {
+    fprintf(stderr, "FAIL %s: %d, not %d\n", what, got, want);
+    ++g_fail;
+  }
+}
+
+// refused with exactly `code` and a message that names the check
+static void expect_rc(const char* what, int rc, int code, const char* needle) {
+  expect_err(what, rc);
+  expect_msg(what, needle);
+  expect_eq(what, rc, code);
+}
+
+// dev switch of the forward, outside include/jmt.h (csrc/attn.hip)
+extern "C" int jmt_attn_set_fwd_rows(int on);
+
 int main() {
   if (jmt_abi_version() != JMT_ABI_VERSION) {
     fprintf(stderr, "FAIL abi version\n");
@@ -225,6 +242,138 @@ int main() {
                                               algn, 512, 512, algn, 512, 512, algn, 512, 512,
                                               algn, 512, 512, fnull, algn, algn, 300, nullptr,
                                               0, 0, 0.1f, nullptr));
+  // The ranges of the attention kernels (jmt_attn_*_ok): one geometry just inside and one just
+  // outside each limit of include/jmt.h, the expected answers as literals; the entry point
+  // refuses every outside geometry (aligned dummy operands) before a launch.
+  {
+    const int64_t S20 = 1 << 20, S23 = 1 << 23;   // 1024 rows x 2^20 x 2 B = 128 x 2^23 x 2 B = 2 GiB
+    const int id2[2] = {0, 1};
+#define FWD_SQ(N, H, Lq, Lk, sk, sv, spp)                                                     \
+    jmt_attn_fwd_sq(JMT_BF16, N, H, Lq, Lk, 512, algn, 512, 512, algn, sk, 512, algn, sv, 512,  \
+                    algn, 512, 512, 0.1f, fnull, spp, id2, 2, nullptr)
+#define BWD_PDS(N, H, Lq, Lk, ldp, sk, sv)                                                    \
+    jmt_attn_bwd(JMT_BF16, N, H, Lq, Lk, 512, algn, 512, 512, algn, 512, 512, algn, 512, 512,   \
+                 algn, sk, 512, algn, sv, 512, (const float*)algn, algn, algn, ldp, nullptr, 0, \
+                 0, 0.1f, nullptr)
+#define DKDV(N, H, Lq, Lk, ldp, sgo, sq, sk, sdk, sdv, sdq, dq)                               \
+    jmt_attn_dkdv(JMT_BF16, N, H, Lq, Lk, 512, algn, algn, ldp, algn, sgo, 512, algn, sq, 512,  \
+                  algn, sk, 512, algn, sdk, 512, algn, sdv, 512, (dq) ? algn : nullptr, sdq,    \
+                  512, nullptr)
+    // whole-row forward: Lq > 64, Lk K / V rows below 2 GiB, items, the forward-rows switch
+    expect_eq("fwd_rows Lq 65", jmt_attn_fwd_rows_ok(2, 1, 65, 300, 512, 512), 1);
+    expect_eq("fwd_rows Lq 64", jmt_attn_fwd_rows_ok(2, 1, 64, 300, 512, 512), 0);
+    expect_rc("fwd_sq Lq 64", FWD_SQ(2, 1, 64, 300, 512, 512, 1), JMT_ERR_UNSUPPORTED, "whole-row");
+    expect_eq("fwd_rows K in", jmt_attn_fwd_rows_ok(2, 1, 300, 1024, S20 - 8, 512), 1);
+    expect_eq("fwd_rows K out", jmt_attn_fwd_rows_ok(2, 1, 300, 1024, S20, 512), 0);
+    expect_rc("fwd_sq K out", FWD_SQ(2, 1, 300, 1024, S20, 512, 1), JMT_ERR_UNSUPPORTED,
+              "whole-row");
+    expect_eq("fwd_rows V in", jmt_attn_fwd_rows_ok(2, 1, 300, 1024, 512, S20 - 8), 1);
+    expect_eq("fwd_rows V out", jmt_attn_fwd_rows_ok(2, 1, 300, 1024, 512, S20), 0);
+    expect_rc("fwd_sq V out", FWD_SQ(2, 1, 300, 1024, 512, S20, 1), JMT_ERR_UNSUPPORTED,
+              "whole-row");
+    expect_eq("fwd_rows items in", jmt_attn_fwd_rows_ok((1 << 24) - 2, 128, 65, 300, 512, 512), 1);
+    expect_eq("fwd_rows items out", jmt_attn_fwd_rows_ok(1 << 24, 128, 65, 300, 512, 512), 0);
+    expect_rc("fwd_sq items out", FWD_SQ(1 << 24, 128, 65, 300, 512, 512, 1 << 23), JMT_ERR_ARG,
+              "bad sizes");
+    jmt_attn_set_fwd_rows(0);
+    expect_eq("fwd_rows switched off", jmt_attn_fwd_rows_ok(2, 1, 300, 300, 512, 512), 0);
+    expect_rc("fwd_sq switched off", FWD_SQ(2, 1, 300, 300, 512, 512, 1), JMT_ERR_UNSUPPORTED,
+              "whole-row");
+    jmt_attn_set_fwd_rows(-1);
+    expect_eq("fwd_rows switch reset", jmt_attn_fwd_rows_ok(2, 1, 300, 300, 512, 512), 1);
+    // P / dS backward: ldp a multiple of 32 covering Lk, (Lq + 128) ldp 16-bit values below
+    // 1 GiB, Lk K / V rows below 2 GiB
+    expect_eq("pds in", jmt_attn_bwd_pds_ok(2, 1, 300, 300, 320, 512, 512), 1);
+    expect_eq("pds ldp % 32", jmt_attn_bwd_pds_ok(2, 1, 300, 300, 328, 512, 512), 0);
+    expect_rc("bwd pds ldp % 32", BWD_PDS(2, 1, 300, 300, 328, 512, 512), JMT_ERR_ARG, "ldp");
+    expect_eq("pds ldp cover in", jmt_attn_bwd_pds_ok(2, 1, 300, 289, 320, 512, 512), 1);
+    expect_eq("pds ldp cover out", jmt_attn_bwd_pds_ok(2, 1, 300, 321, 320, 512, 512), 0);
+    expect_rc("bwd pds ldp cover", BWD_PDS(2, 1, 300, 321, 320, 512, 512), JMT_ERR_ARG, "ldp");
+    expect_eq("pds 1 GiB in", jmt_attn_bwd_pds_ok(1, 1, 16255, 300, 32768, 512, 512), 1);
+    expect_eq("pds 1 GiB out", jmt_attn_bwd_pds_ok(1, 1, 16256, 300, 32768, 512, 512), 0);
+    expect_rc("bwd pds 1 GiB", BWD_PDS(1, 1, 16256, 300, 32768, 512, 512), JMT_ERR_ARG, "1 GiB");
+    expect_eq("pds K in", jmt_attn_bwd_pds_ok(1, 1, 300, 1024, 1024, S20 - 8, 512), 1);
+    expect_eq("pds K out", jmt_attn_bwd_pds_ok(1, 1, 300, 1024, 1024, S20, 512), 0);
+    expect_rc("bwd pds K", BWD_PDS(1, 1, 300, 1024, 1024, S20, 512), JMT_ERR_ARG, "2 GiB");
+    expect_eq("pds V out", jmt_attn_bwd_pds_ok(1, 1, 300, 1024, 1024, 512, S20), 0);
+    expect_rc("bwd pds V", BWD_PDS(1, 1, 300, 1024, 1024, 512, S20), JMT_ERR_ARG, "2 GiB");
+    expect_eq("pds items in", jmt_attn_bwd_pds_ok((1 << 24) - 2, 128, 65, 33, 64, 512, 512), 1);
+    expect_eq("pds items out", jmt_attn_bwd_pds_ok(1 << 24, 128, 65, 33, 64, 512, 512), 0);
+    expect_rc("bwd pds items", BWD_PDS(1 << 24, 128, 65, 33, 64, 512, 512), JMT_ERR_ARG,
+              "bad sizes");
+    // dK / dV (/ dQ)
+    expect_eq("dkdv in", jmt_attn_dkdv_ok(2, 1, 300, 300, 384, 512, 512, 512, 512, 512, 512, 1), 1);
+    expect_eq("dkdv in, no dq", jmt_attn_dkdv_ok(2, 1, 300, 300, 384, 512, 512, 0, 512, 512, 0, 0), 1);
+    expect_eq("dkdv ldp cover", jmt_attn_dkdv_ok(2, 1, 300, 300, 320, 512, 512, 0, 512, 512, 0, 0), 0);
+    expect_rc("dkdv ldp cover", DKDV(2, 1, 300, 300, 320, 512, 512, 0, 512, 512, 0, 0), JMT_ERR_ARG,
+              "128-key tiles");
+    expect_eq("dkdv dK stride in",
+              jmt_attn_dkdv_ok(2, 1, 300, 300, 384, 512, 512, 0, S23 - 8, S23 - 8, 0, 0), 1);
+    expect_eq("dkdv dK stride out",
+              jmt_attn_dkdv_ok(2, 1, 300, 300, 384, 512, 512, 0, S23, 512, 0, 0), 0);
+    expect_rc("dkdv dK stride out", DKDV(2, 1, 300, 300, 384, 512, 512, 0, S23, 512, 0, 0),
+              JMT_ERR_ARG, "dK / dV row stride");
+    expect_eq("dkdv dV stride out",
+              jmt_attn_dkdv_ok(2, 1, 300, 300, 384, 512, 512, 0, 512, S23, 0, 0), 0);
+    expect_eq("dkdv dK stride below the heads",
+              jmt_attn_dkdv_ok(2, 2, 300, 300, 384, 1024, 1024, 0, 1016, 1024, 0, 0), 0);
+    expect_rc("dkdv dK stride below the heads",
+              DKDV(2, 2, 300, 300, 384, 1024, 1024, 0, 1016, 1024, 0, 0), JMT_ERR_ARG,
+              "dK / dV row stride");
+    expect_eq("dkdv dQ stride in",
+              jmt_attn_dkdv_ok(2, 1, 300, 300, 384, 512, 512, 512, 512, 512, S23 - 8, 1), 1);
+    expect_eq("dkdv dQ stride out",
+              jmt_attn_dkdv_ok(2, 1, 300, 300, 384, 512, 512, 512, 512, 512, S23, 1), 0);
+    expect_eq("dkdv dQ stride unused",
+              jmt_attn_dkdv_ok(2, 1, 300, 300, 384, 512, 512, 512, 512, 512, S23, 0), 1);
+    expect_rc("dkdv dQ stride out", DKDV(2, 1, 300, 300, 384, 512, 512, 512, 512, 512, S23, 1),
+              JMT_ERR_ARG, "dQ / K row stride");
+    expect_eq("dkdv K rows in",
+              jmt_attn_dkdv_ok(1, 1, 300, 1024, 1024, 512, 512, S20 - 8, 512, 512, 512, 1), 1);
+    expect_eq("dkdv K rows out",
+              jmt_attn_dkdv_ok(1, 1, 300, 1024, 1024, 512, 512, S20, 512, 512, 512, 1), 0);
+    expect_rc("dkdv K rows out", DKDV(1, 1, 300, 1024, 1024, 512, 512, S20, 512, 512, 512, 1),
+              JMT_ERR_ARG, "dQ / K row stride");
+    expect_eq("dkdv ldp % 32, no dq",
+              jmt_attn_dkdv_ok(2, 1, 300, 300, 392, 512, 512, 0, 512, 512, 0, 0), 1);
+    expect_eq("dkdv ldp % 32",
+              jmt_attn_dkdv_ok(2, 1, 300, 300, 392, 512, 512, 512, 512, 512, 512, 1), 0);
+    expect_eq("dkdv dO rows in",
+              jmt_attn_dkdv_ok(1, 1, 1024, 300, 384, S20 - 8, 512, 0, 512, 512, 0, 0), 1);
+    expect_eq("dkdv dO rows out",
+              jmt_attn_dkdv_ok(1, 1, 1024, 300, 384, S20, 512, 0, 512, 512, 0, 0), 0);
+    expect_rc("dkdv dO rows out", DKDV(1, 1, 1024, 300, 384, S20, 512, 0, 512, 512, 0, 0),
+              JMT_ERR_ARG, "exceed 2 GiB");
+    expect_eq("dkdv Q rows out",
+              jmt_attn_dkdv_ok(1, 1, 1024, 300, 384, 512, S20, 0, 512, 512, 0, 0), 0);
+    expect_eq("dkdv P rows in",
+              jmt_attn_dkdv_ok(1, 1, 32767, 32768, 32768, 512, 512, 0, 512, 512, 0, 0), 1);
+    expect_eq("dkdv P rows out",
+              jmt_attn_dkdv_ok(1, 1, 32768, 32768, 32768, 512, 512, 0, 512, 512, 0, 0), 0);
+    // items of the planned tile: Lq = Lk = 300 with dQ is 6 items of 160 rows per head (9 of
+    // 128), Lq = Lk = 128 with dQ 3 of 128, without dQ 2
+    expect_eq("dkdv items in, 160 rows",
+              jmt_attn_dkdv_ok(357913941, 1, 300, 300, 384, 512, 512, 512, 512, 512, 512, 1), 1);
+    expect_eq("dkdv items out, 160 rows",
+              jmt_attn_dkdv_ok(357913942, 1, 300, 300, 384, 512, 512, 512, 512, 512, 512, 1), 0);
+    expect_rc("dkdv items out, 160 rows",
+              DKDV(357913942, 1, 300, 300, 384, 512, 512, 512, 512, 512, 512, 1), JMT_ERR_ARG,
+              "too many items");
+    expect_eq("dkdv items in, 128 rows",
+              jmt_attn_dkdv_ok(715827882, 1, 128, 128, 128, 512, 512, 512, 512, 512, 512, 1), 1);
+    expect_eq("dkdv items out, 128 rows",
+              jmt_attn_dkdv_ok(715827883, 1, 128, 128, 128, 512, 512, 512, 512, 512, 512, 1), 0);
+    expect_eq("dkdv items in, no dq",
+              jmt_attn_dkdv_ok((1 << 30) - 1, 1, 128, 128, 128, 512, 512, 0, 512, 512, 0, 0), 1);
+    expect_eq("dkdv items out, no dq",
+              jmt_attn_dkdv_ok(1 << 30, 1, 128, 128, 128, 512, 512, 0, 512, 512, 0, 0), 0);
+    expect_rc("dkdv items out, no dq",
+              DKDV(1 << 30, 1, 128, 128, 128, 512, 512, 0, 512, 512, 0, 0), JMT_ERR_ARG,
+              "too many items");
+#undef FWD_SQ
+#undef BWD_PDS
+#undef DKDV
+  }
   // shared queries: the table is checked before anything else of the launch
   {
     const int id2[2] = {0, 1}, fwd[2] = {1, 1}, chain[3] = {0, 0, 1}, three[3] = {0, 0, 0};

@@ -1124,17 +1124,32 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
   }
 }
 
-template <typename K>
-static void set_lds(K fn, int bytes) {
-  (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+// ---- the kernels' ranges (host only: sizes and row strides, no pointer).  The entry points
+// validate with these and the jmt_attn_*_ok exports answer from them, so a limit is written once.
+// qt: query rows per item of the kernel the caller launches (the item count must fit an int)
+static bool sizes_ok(int N, int H, int Lq, int Lk, int qt) {
+  return N > 0 && H > 0 && Lq > 0 && Lk > 0 &&
+         (int64_t)N * H * ((Lq + qt - 1) / qt) < (1LL << 31);
+}
+// L rows of row stride s (16-bit elements) within 32-bit byte offsets
+static bool rows_fit(int64_t L, int64_t s) { return L * s * 2 < (1LL << 31); }
+
+// nullptr when the P / dS kernel (jmt_attn_bwd with dq == NULL) takes these sizes and strides,
+// else what is out of range
+static const char* pds_range(int N, int H, int Lq, int Lk, int64_t ldp, int64_t sk_l,
+                             int64_t sv_l) {
+  if (!sizes_ok(N, H, Lq, Lk, AP_QT)) return "bad sizes";
+  if (ldp < (int64_t)(Lk + AP_KT - 1) / AP_KT * AP_KT || ldp % AP_KT != 0)
+    return "ldp must be a multiple of 32 covering Lk";
+  if ((int64_t)(Lq + AP_QT) * ldp * 2 >= (1LL << 30))
+    return "Lq + 128 rows of ldp 16-bit values must stay below 1 GiB";
+  if (!rows_fit(Lk, sk_l) || !rows_fit(Lk, sv_l)) return "Lk K / V rows must stay below 2 GiB";
+  return nullptr;
 }
 
-// qt: query rows per item of the kernel the caller launches (the item count must fit an int)
 static int check_common(const char* name, int N, int H, int Lq, int Lk, int qt,
                         const void* const* ptrs, int nptr, const int64_t* strides, int nstr) {
-  JMT_CHECK_ARG(N > 0 && H > 0 && Lq > 0 && Lk > 0 &&
-                    (int64_t)N * H * ((Lq + qt - 1) / qt) < (1LL << 31),
-                "%s: bad sizes", name);
+  JMT_CHECK_ARG(sizes_ok(N, H, Lq, Lk, qt), "%s: bad sizes", name);
   for (int i = 0; i < nptr; ++i)
     JMT_CHECK_ARG(ptrs[i] != nullptr && ((uintptr_t)ptrs[i] & 15) == 0,
                   "%s: operand %d null or not 16-B aligned", name, i);
@@ -1156,20 +1171,6 @@ using namespace jmt;
 // 1|2|8, backward 1|2|4).
 constexpr int ATTN_FWD_OPT = 11;
 constexpr int ATTN_BWD_OPT = 7;
-
-template <int OPT>
-static void launch_fwd_bf16(dim3 grid, hipStream_t st, const AttnFwdArgs& a) {
-  static bool once = (set_lds(attn_fwd_kernel<__bf16, false, OPT>, AF_LDS), true);
-  (void)once;
-  hipLaunchKernelGGL((attn_fwd_kernel<__bf16, false, OPT>), grid, dim3(512), (size_t)AF_LDS, st,
-                     a);
-}
-template <int OPT>
-static void launch_bwd_bf16(dim3 grid, hipStream_t st, const AttnBwdArgs& a) {
-  static bool once = (set_lds(attn_bwd_kernel<__bf16, OPT>, AB_LDS), true);
-  (void)once;
-  hipLaunchKernelGGL((attn_bwd_kernel<__bf16, OPT>), grid, dim3(512), (size_t)AB_LDS, st, a);
-}
 
 // one block per CU (the 160 KiB of LDS admit one), rounded down to a multiple of 8 (XCDs), when
 // there are more items than CUs; otherwise one block per item
@@ -1221,6 +1222,22 @@ extern "C" int jmt_attn_supported(int dt, int dh) {
   return (dt == JMT_BF16 || dt == JMT_F16) && dh == AT_DH;
 }
 
+// The whole-row kernel (128-row items) takes Lq > 64 when its 32-bit K / V row offsets fit;
+// Lq <= 64 stays on the 64-row kernel, whose arithmetic jmt_attn_short_fwd reproduces bit for
+// bit (include/jmt.h).
+static bool fwd_rows(int Lq, int Lk, int64_t sk_l, int64_t sv_l) {
+  return fwd_rows_on() && Lq > AT_QT && rows_fit(Lk, sk_l) && rows_fit(Lk, sv_l);
+}
+
+extern "C" int jmt_attn_fwd_rows_ok(int N, int H, int Lq, int Lk, int64_t sk_l, int64_t sv_l) {
+  return fwd_rows(Lq, Lk, sk_l, sv_l) && sizes_ok(N, H, Lq, Lk, AR_QT);
+}
+
+extern "C" int jmt_attn_bwd_pds_ok(int N, int H, int Lq, int Lk, int64_t ldp, int64_t sk_l,
+                                   int64_t sv_l) {
+  return pds_range(N, H, Lq, Lk, ldp, sk_l, sv_l) == nullptr;
+}
+
 // jmt_attn_fwd (qs == NULL) and jmt_attn_fwd_sq (qs: the packed query table; the whole-row
 // kernel only)
 static int attn_fwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
@@ -1233,11 +1250,7 @@ static int attn_fwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const voi
                      dt, dh);
   const void* ptrs[] = {q, k, v, o};
   const int64_t strides[] = {sq_l, sq_n, sk_l, sk_n, sv_l, sv_n, so_l, so_n};
-  // The whole-row kernel (128-row items) takes Lq > 64 when its 32-bit K / V row offsets fit;
-  // Lq <= 64 stays on the 64-row kernel, whose arithmetic jmt_attn_short_fwd reproduces bit for
-  // bit (include/jmt.h).
-  const bool rows = fwd_rows_on() && Lq > AT_QT && (int64_t)Lk * sk_l * 2 < (1LL << 31) &&
-                    (int64_t)Lk * sv_l * 2 < (1LL << 31);
+  const bool rows = fwd_rows(Lq, Lk, sk_l, sv_l);
   if (qs && !rows)
     return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_fwd_sq: the whole-row kernel only (Lq > %d, "
                                           "Lk K / V rows below 2 GiB, JMT_ATTN_FWD_ROWS on)",
@@ -1255,76 +1268,36 @@ static int attn_fwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const voi
   hipStream_t st = as_stream(stream);
   a.nitems = ((Lq + qt - 1) / qt) * N * H;
   const dim3 grid(persistent_grid(a.nitems));
-  if (rows) {
+  const char* name = qs ? "jmt_attn_fwd_sq" : "jmt_attn_fwd";
 #if JMT_DIAG
-    static const int dbg =
-        getenv("JMT_ATTN_FWD_ROWS_DBG") ? atoi(getenv("JMT_ATTN_FWD_ROWS_DBG")) : 0;
-    if (dbg && dt == JMT_BF16) {
-#define JMT_ROWS_DBG(D)                                                                      \
-  case D: {                                                                                  \
-    static bool once = (set_lds(attn_fwd_rows_kernel<__bf16, D>, AR_LDS), true);             \
-    (void)once;                                                                              \
-    hipLaunchKernelGGL((attn_fwd_rows_kernel<__bf16, D>), grid, dim3(512), (size_t)AR_LDS,  \
-                       st, a);                                                               \
-  } break;
-      switch (dbg) {
-        JMT_ROWS_DBG(2) JMT_ROWS_DBG(4) JMT_ROWS_DBG(8) JMT_ROWS_DBG(16) JMT_ROWS_DBG(32)
-        JMT_ROWS_DBG(18) JMT_ROWS_DBG(22) JMT_ROWS_DBG(54) JMT_ROWS_DBG(62)
-        default: return set_error(JMT_ERR_ARG, "JMT_ATTN_FWD_ROWS_DBG=%d not built", dbg);
-      }
+  static const int dbg =
+      getenv("JMT_ATTN_FWD_ROWS_DBG") ? atoi(getenv("JMT_ATTN_FWD_ROWS_DBG")) : 0;
+  if (rows && dbg && dt == JMT_BF16) {
+#define JMT_ROWS_DBG(D) \
+  case D: attn_launch<attn_fwd_rows_kernel<__bf16, D>, AR_LDS>(grid, st, a); break;
+    switch (dbg) {
+      JMT_ROWS_DBG(2) JMT_ROWS_DBG(4) JMT_ROWS_DBG(8) JMT_ROWS_DBG(16) JMT_ROWS_DBG(32)
+      JMT_ROWS_DBG(18) JMT_ROWS_DBG(22) JMT_ROWS_DBG(54) JMT_ROWS_DBG(62)
+      default: return set_error(JMT_ERR_ARG, "JMT_ATTN_FWD_ROWS_DBG=%d not built", dbg);
+    }
 #undef JMT_ROWS_DBG
-      JMT_LAUNCH_CHECK("jmt_attn_fwd");
-      return JMT_OK;
-    }
-#endif
-    if (qs) {
-      if (dt == JMT_BF16) {
-        static bool once = (set_lds(attn_fwd_rows_kernel<__bf16, 0, true>, AR_LDS), true);
-        (void)once;
-        hipLaunchKernelGGL((attn_fwd_rows_kernel<__bf16, 0, true>), grid, dim3(512),
-                           (size_t)AR_LDS, st, a);
-      } else {
-        static bool once = (set_lds(attn_fwd_rows_kernel<_Float16, 0, true>, AR_LDS), true);
-        (void)once;
-        hipLaunchKernelGGL((attn_fwd_rows_kernel<_Float16, 0, true>), grid, dim3(512),
-                           (size_t)AR_LDS, st, a);
-      }
-      JMT_LAUNCH_CHECK("jmt_attn_fwd_sq");
-      return JMT_OK;
-    }
-    if (dt == JMT_BF16) {
-      static bool once = (set_lds(attn_fwd_rows_kernel<__bf16>, AR_LDS), true);
-      (void)once;
-      hipLaunchKernelGGL((attn_fwd_rows_kernel<__bf16>), grid, dim3(512), (size_t)AR_LDS, st, a);
-    } else {
-      static bool once = (set_lds(attn_fwd_rows_kernel<_Float16>, AR_LDS), true);
-      (void)once;
-      hipLaunchKernelGGL((attn_fwd_rows_kernel<_Float16>), grid, dim3(512), (size_t)AR_LDS, st,
-                         a);
-    }
     JMT_LAUNCH_CHECK("jmt_attn_fwd");
     return JMT_OK;
   }
-#if JMT_DIAG
-  if (g_stamps && dt == JMT_BF16) {   // diagnostic: phase stamps (jmt_attn_set_stamps)
+  if (!rows && g_stamps && dt == JMT_BF16) {   // diagnostic: phase stamps (jmt_attn_set_stamps)
     a.stamps = (uint64_t*)g_stamps;
-    static bool once = (set_lds(attn_fwd_kernel<__bf16, true, ATTN_FWD_OPT>, AF_LDS), true);
-    (void)once;
-    hipLaunchKernelGGL((attn_fwd_kernel<__bf16, true, ATTN_FWD_OPT>), grid, dim3(512),
-                       (size_t)AF_LDS, st, a);
+    attn_launch<attn_fwd_kernel<__bf16, true, ATTN_FWD_OPT>, AF_LDS>(grid, st, a);
     JMT_LAUNCH_CHECK("jmt_attn_fwd");
     return JMT_OK;
   }
 #endif
-  if (dt == JMT_BF16) {
-    launch_fwd_bf16<ATTN_FWD_OPT>(grid, st, a);
-  } else {
-    static bool once = (set_lds(attn_fwd_kernel<_Float16, false, ATTN_FWD_OPT>, AF_LDS), true);
-    (void)once;
-    hipLaunchKernelGGL((attn_fwd_kernel<_Float16, false, ATTN_FWD_OPT>), grid, dim3(512),
-                       (size_t)AF_LDS, st, a);
-  }
-  JMT_LAUNCH_CHECK("jmt_attn_fwd");
+  by_elem(dt, [&](auto e) {
+    using T = typename decltype(e)::type;
+    if (!rows) attn_launch<attn_fwd_kernel<T, false, ATTN_FWD_OPT>, AF_LDS>(grid, st, a);
+    else if (qs) attn_launch<attn_fwd_rows_kernel<T, 0, true>, AR_LDS>(grid, st, a);
+    else attn_launch<attn_fwd_rows_kernel<T>, AR_LDS>(grid, st, a);
+  });
+  JMT_LAUNCH_CHECK(name);
   return JMT_OK;
 }
 
@@ -1368,100 +1341,54 @@ static int attn_bwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const voi
   const int64_t strides[] = {sgo_l, sgo_n, so_l, so_n, sq_l, sq_n, sk_l, sk_n, sv_l, sv_n, ldp,
                              sdq_l, sdq_n};
   const bool pds = dq == nullptr;                 // P / dS only: dQ left to jmt_attn_dkdv
-  int rc = check_common("jmt_attn_bwd", N, H, Lq, Lk, pds ? AP_QT : AT_QT, ptrs, pds ? 7 : 8,
-                        strides, pds ? 11 : 13);
+  const int qt = pds ? AP_QT : AT_QT;
+  int rc = check_common("jmt_attn_bwd", N, H, Lq, Lk, qt, ptrs, pds ? 7 : 8, strides,
+                        pds ? 11 : 13);
   if (rc != JMT_OK) return rc;
   JMT_CHECK_ARG(lse && ldp >= Lk, "jmt_attn_bwd: lse missing or ldp < Lk");
   if (pds) {
-    JMT_CHECK_ARG(ldp >= (int64_t)(Lk + AP_KT - 1) / AP_KT * AP_KT && ldp % AP_KT == 0 &&
-                      (int64_t)(Lq + AP_QT) * ldp * 2 < (1LL << 30) &&
-                      (int64_t)Lk * sk_l * 2 < (1LL << 31) && (int64_t)Lk * sv_l * 2 < (1LL << 31),
-                  "jmt_attn_bwd (dq = NULL): ldp must be a multiple of 32 covering Lk, Lq rows "
-                  "of ldp 16-bit values below 1 GiB and Lk K / V rows below 2 GiB");
-    AttnBwdArgs a = {};
-    if (qs) a.qs = *qs;
-    a.go = go; a.o = o; a.q = q; a.k = k; a.v = v; a.lse = lse;
-    a.pbuf = p_out; a.dsbuf = ds_out; a.dq = nullptr;
-    a.sgo_l = sgo_l; a.sgo_n = sgo_n; a.so_l = so_l; a.so_n = so_n; a.sq_l = sq_l; a.sq_n = sq_n;
-    a.sk_l = sk_l; a.sk_n = sk_n; a.sv_l = sv_l; a.sv_n = sv_n;
-    a.ldp = ldp;
-    a.Lq = Lq; a.Lk = Lk; a.H = H;
-    a.scale = scale;
-    a.scale_log2 = scale * 1.4426950408889634f;
-    a.nitems = ((Lq + AP_QT - 1) / AP_QT) * N * H;
-    const dim3 grid(persistent_grid(a.nitems));
-    hipStream_t st = as_stream(stream);
-#if JMT_DIAG
-    static const int dbg = getenv("JMT_ATTN_PDS_DBG") ? atoi(getenv("JMT_ATTN_PDS_DBG")) : 0;
-    if (dbg && dt == JMT_BF16) {
-      if (dbg & 64) a.dq = g_stamps;              // the stamps buffer (jmt_attn_set_stamps)
-#define JMT_PDS_DBG(D)                                                                       \
-  case D: {                                                                                  \
-    static bool once = (set_lds(attn_bwd_pds_kernel<__bf16, D>, AP_LDS), true);             \
-    (void)once;                                                                              \
-    hipLaunchKernelGGL((attn_bwd_pds_kernel<__bf16, D>), grid, dim3(512), (size_t)AP_LDS, st, \
-                       a);                                                                   \
-  } break;
-      switch (dbg) {
-        JMT_PDS_DBG(1) JMT_PDS_DBG(2) JMT_PDS_DBG(3) JMT_PDS_DBG(4) JMT_PDS_DBG(6)
-        JMT_PDS_DBG(7) JMT_PDS_DBG(8) JMT_PDS_DBG(15) JMT_PDS_DBG(16) JMT_PDS_DBG(32)
-        JMT_PDS_DBG(17) JMT_PDS_DBG(18) JMT_PDS_DBG(64)
-        default: return set_error(JMT_ERR_ARG, "JMT_ATTN_PDS_DBG=%d not built", dbg);
-      }
-#undef JMT_PDS_DBG
-      JMT_LAUNCH_CHECK("jmt_attn_bwd");
-      return JMT_OK;
-    }
-#endif
-    if (qs) {
-      if (dt == JMT_BF16) {
-        static bool once = (set_lds(attn_bwd_pds_kernel<__bf16, 0, true>, AP_LDS), true);
-        (void)once;
-        hipLaunchKernelGGL((attn_bwd_pds_kernel<__bf16, 0, true>), grid, dim3(512),
-                           (size_t)AP_LDS, st, a);
-      } else {
-        static bool once = (set_lds(attn_bwd_pds_kernel<_Float16, 0, true>, AP_LDS), true);
-        (void)once;
-        hipLaunchKernelGGL((attn_bwd_pds_kernel<_Float16, 0, true>), grid, dim3(512),
-                           (size_t)AP_LDS, st, a);
-      }
-      JMT_LAUNCH_CHECK("jmt_attn_bwd_sq");
-      return JMT_OK;
-    }
-    if (dt == JMT_BF16) {
-      static bool once = (set_lds(attn_bwd_pds_kernel<__bf16>, AP_LDS), true);
-      (void)once;
-      hipLaunchKernelGGL((attn_bwd_pds_kernel<__bf16>), grid, dim3(512), (size_t)AP_LDS, st, a);
-    } else {
-      static bool once = (set_lds(attn_bwd_pds_kernel<_Float16>, AP_LDS), true);
-      (void)once;
-      hipLaunchKernelGGL((attn_bwd_pds_kernel<_Float16>), grid, dim3(512), (size_t)AP_LDS, st,
-                         a);
-    }
-    JMT_LAUNCH_CHECK("jmt_attn_bwd");
-    return JMT_OK;
+    const char* why = pds_range(N, H, Lq, Lk, ldp, sk_l, sv_l);
+    JMT_CHECK_ARG(!why, "jmt_attn_bwd (dq = NULL): %s", why);
   }
   AttnBwdArgs a = {};
+  if (qs) a.qs = *qs;
   a.go = go; a.o = o; a.q = q; a.k = k; a.v = v; a.lse = lse;
   a.pbuf = p_out; a.dsbuf = ds_out; a.dq = dq;
   a.sgo_l = sgo_l; a.sgo_n = sgo_n; a.so_l = so_l; a.so_n = so_n; a.sq_l = sq_l; a.sq_n = sq_n;
-  a.sk_l = sk_l; a.sk_n = sk_n; a.sv_l = sv_l; a.sv_n = sv_n; a.sdq_l = sdq_l; a.sdq_n = sdq_n;
+  a.sk_l = sk_l; a.sk_n = sk_n; a.sv_l = sv_l; a.sv_n = sv_n;
+  if (!pds) { a.sdq_l = sdq_l; a.sdq_n = sdq_n; }
   a.ldp = ldp;
   a.Lq = Lq; a.Lk = Lk; a.H = H;
   a.scale = scale;
   a.scale_log2 = scale * 1.4426950408889634f;
-  a.nitems = ((Lq + AT_QT - 1) / AT_QT) * N * H;
+  a.nitems = ((Lq + qt - 1) / qt) * N * H;
   const dim3 grid(persistent_grid(a.nitems));
   hipStream_t st = as_stream(stream);
-  if (dt == JMT_BF16) {
-    launch_bwd_bf16<ATTN_BWD_OPT>(grid, st, a);
-  } else {
-    static bool once = (set_lds(attn_bwd_kernel<_Float16, ATTN_BWD_OPT>, AB_LDS), true);
-    (void)once;
-    hipLaunchKernelGGL((attn_bwd_kernel<_Float16, ATTN_BWD_OPT>), grid, dim3(512),
-                       (size_t)AB_LDS, st, a);
+  const char* name = qs ? "jmt_attn_bwd_sq" : "jmt_attn_bwd";
+#if JMT_DIAG
+  static const int dbg = getenv("JMT_ATTN_PDS_DBG") ? atoi(getenv("JMT_ATTN_PDS_DBG")) : 0;
+  if (pds && dbg && dt == JMT_BF16) {
+    if (dbg & 64) a.dq = g_stamps;              // the stamps buffer (jmt_attn_set_stamps)
+#define JMT_PDS_DBG(D) \
+  case D: attn_launch<attn_bwd_pds_kernel<__bf16, D>, AP_LDS>(grid, st, a); break;
+    switch (dbg) {
+      JMT_PDS_DBG(1) JMT_PDS_DBG(2) JMT_PDS_DBG(3) JMT_PDS_DBG(4) JMT_PDS_DBG(6)
+      JMT_PDS_DBG(7) JMT_PDS_DBG(8) JMT_PDS_DBG(15) JMT_PDS_DBG(16) JMT_PDS_DBG(32)
+      JMT_PDS_DBG(17) JMT_PDS_DBG(18) JMT_PDS_DBG(64)
+      default: return set_error(JMT_ERR_ARG, "JMT_ATTN_PDS_DBG=%d not built", dbg);
+    }
+#undef JMT_PDS_DBG
+    JMT_LAUNCH_CHECK("jmt_attn_bwd");
+    return JMT_OK;
   }
-  JMT_LAUNCH_CHECK("jmt_attn_bwd");
+#endif
+  by_elem(dt, [&](auto e) {
+    using T = typename decltype(e)::type;
+    if (!pds) attn_launch<attn_bwd_kernel<T, ATTN_BWD_OPT>, AB_LDS>(grid, st, a);
+    else if (qs) attn_launch<attn_bwd_pds_kernel<T, 0, true>, AP_LDS>(grid, st, a);
+    else attn_launch<attn_bwd_pds_kernel<T>, AP_LDS>(grid, st, a);
+  });
+  JMT_LAUNCH_CHECK(name);
   return JMT_OK;
 }
 

@@ -46,6 +46,27 @@ static inline int qshare_pack(const char* name, int N, int spp, const int* tab, 
   return JMT_OK;
 }
 
+// Host side: launch kernel K with LDS bytes of dynamic LDS; the kernel's dynamic-LDS limit is
+// raised once per instantiation.
+template <auto K, int LDS, int BLOCK = 512, typename A>
+static void attn_launch(dim3 grid, hipStream_t st, const A& a) {
+  static bool once = ((void)hipFuncSetAttribute((const void*)K,
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS),
+                      true);
+  (void)once;
+  hipLaunchKernelGGL(K, grid, dim3(BLOCK), (size_t)LDS, st, a);
+}
+// f(Elem<__bf16>{}) or f(Elem<_Float16>{}): the two element types of the fused kernels
+template <typename T>
+struct Elem {
+  using type = T;
+};
+template <typename F>
+static void by_elem(int dt, F f) {
+  if (dt == JMT_BF16) f(Elem<__bf16>{});
+  else f(Elem<_Float16>{});
+}
+
 // arguments of the long-sequence attention backward (attn.hip attn_bwd_kernel)
 struct AttnBwdArgs {
   const void* go;

@@ -607,6 +607,34 @@ static int dkdv_plan(int Lq, int Lk, int64_t sdk_l, int64_t sdv_l, int64_t sdq_l
   return dkdv_cost(Lq, Lk, 160) < dkdv_cost(Lq, Lk, 128) ? 160 : 128;   // ties keep 128
 }
 
+// nullptr when jmt_attn_dkdv takes these sizes and row strides (host only, no pointer: the entry
+// point validates with it and jmt_attn_dkdv_ok answers from it), else what is out of range.
+// sk_l / sdq_l count with has_dq only.
+static const char* dkdv_range(int N, int H, int Lq, int Lk, int64_t ldp, int64_t sgo_l,
+                              int64_t sq_l, int64_t sk_l, int64_t sdk_l, int64_t sdv_l,
+                              int64_t sdq_l, bool has_dq) {
+  constexpr int64_t DK_KT = DkGeo<8>::KT;              // the contract's tile: ldp, stride ranges
+  constexpr int64_t LIM = 1LL << 31;                   // 32-bit byte offsets of 16-bit elements
+  if (!(N > 0 && H > 0 && Lq > 0 && Lk > 0)) return "bad sizes";
+  if (ldp < (Lk + DK_KT - 1) / DK_KT * DK_KT) return "ldp must cover 128-key tiles";
+  if (sdk_l < H * AT_DH || sdv_l < H * AT_DH || DK_KT * sdk_l * 2 >= LIM ||
+      DK_KT * sdv_l * 2 >= LIM)
+    return "dK / dV row stride out of range";
+  if (has_dq) {
+    if (sdq_l < H * AT_DH || DK_KT * sdq_l * 2 >= LIM || Lk * sk_l * 2 >= LIM)
+      return "dQ / K row stride out of range";
+    // the tile-major region of head nh starts at nh Lq ldp: whole 32-key tiles only
+    if (ldp % 32 != 0) return "tile-major P / dS need ldp % 32 == 0";
+  }
+  const int kt = dkdv_plan(Lq, Lk, sdk_l, sdv_l, has_dq ? sdq_l : 0, has_dq);
+  const int nkt = (Lk + kt - 1) / kt;
+  const int nqd = has_dq ? (Lq + kt - 1) / kt : 0;     // dQ items per (n, h)
+  if ((int64_t)N * H * (2 * nkt + nqd) >= LIM) return "too many items";
+  if (Lq * sgo_l * 2 >= LIM || Lq * sq_l * 2 >= LIM || Lq * ldp * 2 >= LIM)
+    return "Lq rows of dO / Q / P exceed 2 GiB";
+  return nullptr;
+}
+
 template <typename T, int NKG, bool SQ>
 static void dkdv_launch_sq(const AttnDkdvArgs& a, int grid, hipStream_t st) {
   constexpr int lds = DkGeo<NKG>::LDS;
@@ -639,6 +667,13 @@ extern "C" int jmt_attn_dkdv_plan(int Lq, int Lk, int H, int64_t sdk_l, int64_t 
   return dkdv_plan(Lq, Lk, sdk_l, sdv_l, sdq_l, has_dq != 0);
 }
 
+extern "C" int jmt_attn_dkdv_ok(int N, int H, int Lq, int Lk, int64_t ldp, int64_t sgo_l,
+                                int64_t sq_l, int64_t sk_l, int64_t sdk_l, int64_t sdv_l,
+                                int64_t sdq_l, int has_dq) {
+  return dkdv_range(N, H, Lq, Lk, ldp, sgo_l, sq_l, sk_l, sdk_l, sdv_l, sdq_l, has_dq != 0) ==
+         nullptr;
+}
+
 // jmt_attn_dkdv (qs == NULL) and jmt_attn_dkdv_sq (qs: the packed query table of npair pairs;
 // merge: one dQ per shared query, qtab the table qs was packed from)
 static int dkdv_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* p, const void* ds,
@@ -647,12 +682,10 @@ static int dkdv_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* p
                      void* dk, int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l,
                      int64_t sdv_n, void* dq, int64_t sdq_l, int64_t sdq_n, const QShare* qs,
                      const int* qtab, int npair, int merge, void* stream) {
-  constexpr int DK_KT = DkGeo<8>::KT;                  // the contract's tile: ldp, stride ranges
   if (N == 0 || Lk == 0) return JMT_OK;
   if (!((dt == JMT_BF16 || dt == JMT_F16) && dh == AT_DH))
     return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_dkdv: dtype %d / head dim %d not supported",
                      dt, dh);
-  JMT_CHECK_ARG(N > 0 && H > 0 && Lq > 0 && Lk > 0, "jmt_attn_dkdv: bad sizes");
   const void* ptrs[] = {p, ds, go, q, dk, dv};
   for (int i = 0; i < 6; ++i)
     JMT_CHECK_ARG(ptrs[i] != nullptr && ((uintptr_t)ptrs[i] & 15) == 0,
@@ -660,30 +693,16 @@ static int dkdv_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* p
   const int64_t strides[] = {ldp, sgo_l, sgo_n, sq_l, sq_n, sdk_l, sdk_n, sdv_l, sdv_n};
   for (int i = 0; i < 9; ++i)
     JMT_CHECK_ARG(strides[i] % 8 == 0, "jmt_attn_dkdv: stride %d not a multiple of 8", i);
-  JMT_CHECK_ARG(ldp >= (int64_t)((Lk + DK_KT - 1) / DK_KT) * DK_KT,
-                "jmt_attn_dkdv: ldp must cover 128-key tiles (>= %d)",
-                (Lk + DK_KT - 1) / DK_KT * DK_KT);
-  JMT_CHECK_ARG(sdk_l >= H * AT_DH && sdv_l >= H * AT_DH &&
-                    (int64_t)DK_KT * sdk_l * 2 < (1LL << 31) &&
-                    (int64_t)DK_KT * sdv_l * 2 < (1LL << 31),
-                "jmt_attn_dkdv: dK / dV row stride out of range");
-  if (dq) {
+  if (dq)
     JMT_CHECK_ARG(k != nullptr && ((uintptr_t)k & 15) == 0 && ((uintptr_t)dq & 15) == 0 &&
                       sk_l % 8 == 0 && sk_n % 8 == 0 && sdq_l % 8 == 0 && sdq_n % 8 == 0,
                   "jmt_attn_dkdv: k / dq null, misaligned or strides not multiples of 8");
-    JMT_CHECK_ARG(sdq_l >= H * AT_DH && (int64_t)DK_KT * sdq_l * 2 < (1LL << 31) &&
-                      (int64_t)Lk * sk_l * 2 < (1LL << 31),
-                  "jmt_attn_dkdv: dQ / K row stride out of range");
-    // the tile-major region of head nh starts at nh Lq ldp: whole 32-key tiles only
-    JMT_CHECK_ARG(ldp % 32 == 0, "jmt_attn_dkdv: tile-major P / dS need ldp %% 32 == 0");
-  }
+  const char* why = dkdv_range(N, H, Lq, Lk, ldp, sgo_l, sq_l, sk_l, sdk_l, sdv_l, sdq_l,
+                               dq != nullptr);
+  JMT_CHECK_ARG(!why, "jmt_attn_dkdv: %s", why);
   const int kt = dkdv_plan(Lq, Lk, sdk_l, sdv_l, dq ? sdq_l : 0, dq != nullptr);
   const int nkt = (Lk + kt - 1) / kt;
   const int nqd = dq ? (Lq + kt - 1) / kt : 0;          // dQ items per (n, h)
-  JMT_CHECK_ARG((int64_t)N * H * (2 * nkt + nqd) < (1LL << 31), "jmt_attn_dkdv: too many items");
-  JMT_CHECK_ARG((int64_t)Lq * sgo_l * 2 < (1LL << 31) && (int64_t)Lq * sq_l * 2 < (1LL << 31) &&
-                    (int64_t)Lq * ldp * 2 < (1LL << 31),
-                "jmt_attn_dkdv: Lq rows of dO / Q / P exceed 2 GiB");
   AttnDkdvArgs a = {};
   if (qs) a.qs = *qs;
   a.p = p; a.ds = ds; a.go = go; a.q = q; a.k = k; a.dk = dk; a.dv = dv; a.dq = dq;

@@ -293,11 +293,6 @@ __global__ __launch_bounds__(256, 1) void attn_short_bwd_kernel(AttnShortArgs p)
   }
 }
 
-template <typename K>
-static void as_set_lds(K fn, int bytes) {
-  (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 static int as_check(const char* name, int N, int H, int Lq, int Lk, const void* const* ptrs,
                     int nptr, const int64_t* strides, int nstr) {
   JMT_CHECK_ARG(N > 0 && H > 0 && Lq >= 1 && Lq <= AS_L && Lk >= 1 && Lk <= AS_L &&
@@ -343,15 +338,9 @@ extern "C" int jmt_attn_short_fwd(int dt, int N, int H, int Lq, int Lk, int dh, 
   a.scale_log2 = scale * 1.4426950408889634f;
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(N * H));
-  if (dt == JMT_BF16) {
-    static bool once = (as_set_lds(attn_short_fwd_kernel<__bf16>, ASF_LDS), true);
-    (void)once;
-    hipLaunchKernelGGL(attn_short_fwd_kernel<__bf16>, grid, dim3(256), (size_t)ASF_LDS, st, a);
-  } else {
-    static bool once = (as_set_lds(attn_short_fwd_kernel<_Float16>, ASF_LDS), true);
-    (void)once;
-    hipLaunchKernelGGL(attn_short_fwd_kernel<_Float16>, grid, dim3(256), (size_t)ASF_LDS, st, a);
-  }
+  by_elem(dt, [&](auto e) {
+    attn_launch<attn_short_fwd_kernel<typename decltype(e)::type>, ASF_LDS, 256>(grid, st, a);
+  });
   JMT_LAUNCH_CHECK("jmt_attn_short_fwd");
   return JMT_OK;
 }
@@ -387,15 +376,9 @@ extern "C" int jmt_attn_short_bwd(int dt, int N, int H, int Lq, int Lk, int dh, 
   a.scale_log2 = scale * 1.4426950408889634f;
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(N * H));
-  if (dt == JMT_BF16) {
-    static bool once = (as_set_lds(attn_short_bwd_kernel<__bf16>, ASB_LDS), true);
-    (void)once;
-    hipLaunchKernelGGL(attn_short_bwd_kernel<__bf16>, grid, dim3(256), (size_t)ASB_LDS, st, a);
-  } else {
-    static bool once = (as_set_lds(attn_short_bwd_kernel<_Float16>, ASB_LDS), true);
-    (void)once;
-    hipLaunchKernelGGL(attn_short_bwd_kernel<_Float16>, grid, dim3(256), (size_t)ASB_LDS, st, a);
-  }
+  by_elem(dt, [&](auto e) {
+    attn_launch<attn_short_bwd_kernel<typename decltype(e)::type>, ASB_LDS, 256>(grid, st, a);
+  });
   JMT_LAUNCH_CHECK("jmt_attn_short_bwd");
   return JMT_OK;
 }

@@ -122,6 +122,12 @@ _PROTOS = {
                                  C.POINTER(c_int), c_int, c_int, c_vp]),
     # the tile (128 / 160 rows) jmt_attn_dkdv takes: (Lq, Lk, H, sdk_l, sdv_l, sdq_l, has_dq)
     "jmt_attn_dkdv_plan": (c_int, [c_int, c_int, c_int, c_i64, c_i64, c_i64, c_int]),
+    # the kernels' ranges (no GPU call): (N, H, Lq, Lk, sk_l, sv_l), (N, H, Lq, Lk, ldp, sk_l,
+    # sv_l), (N, H, Lq, Lk, ldp, sgo_l, sq_l, sk_l, sdk_l, sdv_l, sdq_l, has_dq)
+    "jmt_attn_fwd_rows_ok": (c_int, [c_int, c_int, c_int, c_int, c_i64, c_i64]),
+    "jmt_attn_bwd_pds_ok": (c_int, [c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64]),
+    "jmt_attn_dkdv_ok": (c_int, [c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                 c_i64, c_i64, c_int]),
     # dev switch outside include/jmt.h: 128 / 160 force the tile where it is valid, 0 the rule,
     # -1 returns to JMT_ATTN_DKDV_KT (csrc/attn_dkdv.hip)
     "jmt_attn_dkdv_set_tile": (c_int, [c_int]),

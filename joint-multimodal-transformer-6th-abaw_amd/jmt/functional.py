@@ -15,11 +15,12 @@ Layout conventions
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
@@ -27,7 +28,7 @@ from torch.autograd.function import once_differentiable
 
 from . import ops
 from . import streams
-from ._lib import F32
+from ._lib import F32, JMTError
 
 # ------------------------------------------------------------------------- precision policy
 _policy = {"dtype": None}
@@ -807,11 +808,11 @@ class AttnCoreFn(Function):
         tensors = ctx.saved_tensors
         meta, owner = ctx.meta
         q_src, k_src, v_src = tensors[:3]
-        cd = meta[7]
+        cd = meta.cd
         # one gradient buffer per distinct source tensor (packed qkv -> one buffer)
         srcs = (q_src, k_src, v_src)
         bufs = [None, None, None]
-        E, cols = meta[0], meta[2:5]
+        E, cols = meta.E, (meta.qcol, meta.kcol, meta.vcol)
         for i in range(3):
             if owner[i] == i:
                 width = srcs[i].shape[-1]
@@ -836,32 +837,76 @@ def _small_aligned(t, col, cd):
             and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0)
 
 
-def attn_shared_ok(q_src, k_src, v_src, E, H, qcol, kcol, vcol) -> bool:
-    """Whether attn_forward / attn_backward take `qshare` for these views (gradient buffers laid
-    out like the sources): the 16-bit fused kernels on the whole-row forward and the P / dS +
-    dK / dV / dQ backward, i.e. every condition under which attn_backward reaches its
-    `pds` branch, and Lq > 64.  Anything else keeps the unshared launches."""
-    cd = compute_dtype()
-    if cd == torch.float32:
-        return False
-    Lq, N = q_src.shape[0], q_src.shape[1]
-    Lk = k_src.shape[0]
+class AttnOperand(NamedTuple):
+    """What attn_plan asks of an operand view: `aligned` as _small_aligned at its column offset,
+    `stride` its row stride in elements."""
+    aligned: bool
+    stride: int
+
+
+def _operand(t, col, cd) -> AttnOperand:
+    return AttnOperand(_small_aligned(t, col, cd), t.stride(0))
+
+
+class AttnPlan(NamedTuple):
+    """fwd: "small" | "short" | "fused" | "gemm" (GEMM + softmax).  rows: the fused forward is
+    the whole-row kernel.  bwd (None while the gradient buffers are unknown): "small" | "short" |
+    "pds_dkdv" (P / dS kernel + attn_dkdv with dQ) | "bwd64_dkdv" (64-row backward with dQ +
+    attn_dkdv) | "bwd64_gemm" (64-row backward + two batched GEMMs) | "gemm".  shared_q: the
+    *_sq launches take the call (whole-row forward and "pds_dkdv")."""
+    fwd: str
+    rows: bool
+    bwd: Optional[str]
+    shared_q: bool
+
+
+# what attn_backward keeps of an attn_forward call besides its tensors (fwd: AttnPlan.fwd)
+AttnMeta = collections.namedtuple("AttnMeta", "E H qcol kcol vcol ldS scale cd fwd")
+
+
+def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=None,
+              fwd=None) -> AttnPlan:
+    """The one place an attention call's kernels are chosen (host only, no tensors).  q .. dv:
+    AttnOperand of each view, the gradient ones (go: dO as attn_backward normalises it) once they
+    exist.  fwd: the forward path already taken (attn_backward; the saved state fixes it).  The
+    switches (ops._attn_fused / _attn_short / _attn_dkdv / _attn_pds, the library's forward-rows
+    switch) are read at every call and the kernels' ranges are asked of the library."""
     dh = E // H
-    aligned = all(_small_aligned(t, c, cd)
-                  for t, c in ((q_src, qcol), (k_src, kcol), (v_src, vcol)))
-    if not aligned or ops.small_attn_ok(E, H, Lq, Lk) or ops.attn_short_ok(_dc(cd), dh, Lq, Lk):
-        return False
-    sq_l, sk_l, sv_l = q_src.stride(0), k_src.stride(0), v_src.stride(0)
-    return (ops.attn_sq_ok(_dc(cd), dh, Lq, Lk, sk_l, sv_l)
-            and ops.attn_dkdv_ok(N, H, Lq, Lk, dh, E, sq_l, sk_l, sv_l)
-            and ops.attn_pds_ok(Lq, Lk, sq_l, max(sk_l, sv_l), H))
+    half = cd != torch.float32
+    if fwd is None:
+        aligned = q.aligned and k.aligned and v.aligned and o.aligned
+        if aligned and ops.small_attn_ok(E, H, Lq, Lk):
+            fwd = "small"
+        elif half and aligned and ops.attn_short_ok(_dc(cd), dh, Lq, Lk):
+            fwd = "short"
+        elif half and ops.attn_supported(_dc(cd), dh):
+            fwd = "fused"
+        else:
+            fwd = "gemm"
+    rows = fwd == "fused" and ops.attn_fwd_rows_ok(N, H, Lq, Lk, k.stride, v.stride)
+    bwd = None
+    if None not in (go, dq, dk, dv):
+        bwd = fwd
+        if fwd == "fused":
+            ldp = ops.attn_dkdv_ldp(Lk)
+            bwd = "bwd64_gemm"
+            if (ops._attn_dkdv["on"] and dk.aligned and dv.aligned and
+                    ops.attn_dkdv_ok(N, H, Lq, Lk, ldp, go.stride, q.stride, dk.stride,
+                                     dv.stride)):
+                bwd = "bwd64_dkdv"
+                if (ops._attn_pds["on"] and dq.aligned and k.aligned and
+                        ops.attn_bwd_pds_ok(N, H, Lq, Lk, ldp, k.stride, v.stride) and
+                        ops.attn_dkdv_ok(N, H, Lq, Lk, ldp, go.stride, q.stride, dk.stride,
+                                         dv.stride, k.stride, dq.stride)):
+                    bwd = "pds_dkdv"
+    return AttnPlan(fwd, rows, bwd, rows and bwd == "pds_dkdv")
 
 
 def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
     """softmax(Q K^T / sqrt(dh)) V on seq-first strided views (see AttnCoreFn).  Returns the
     output (Lq, N, E) (memory order of q_src's rows) and the state attn_backward needs.
     qshare = (spp, qtab): sequence p spp + b reads the Q rows of sequence qtab[p] spp + b
-    (ops.attn_fwd_sq; the caller has asked attn_shared_ok)."""
+    (ops.attn_fwd_sq; the caller has asked attn_plan with its gradient layouts)."""
     cd = compute_dtype()
     for t in (q_src, k_src, v_src):
         assert t.dtype == cd and t.stride(-1) == 1
@@ -873,17 +918,11 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
     bS = (H * Lq * ldS, Lq * ldS)
     scale = 1.0 / math.sqrt(dh)
     o = Rows(q_src).like(E, cd)
-    aligned = all(_small_aligned(t, c, cd)
-                  for t, c in ((q_src, qcol), (k_src, kcol), (v_src, vcol), (o, 0)))
-    small = ops.small_attn_ok(E, H, Lq, Lk) and aligned
-    # Lq, Lk <= 32 (the batch-axis attention of wo_JR, the T = 16 real-data windows): one block
-    # per sequence, and the backward computes dK / dV in the same kernel (attn_short.hip)
-    short = (not small and cd != torch.float32 and aligned and
-             ops.attn_short_ok(_dc(cd), dh, Lq, Lk))
-    fused = "small" if small else ("short" if short else
-                                   (cd != torch.float32 and ops.attn_supported(_dc(cd), dh)))
-    assert qshare is None or fused is True, "attn_forward: qshare on an unsupported shape"
-    if small:
+    plan = attn_plan(cd, N, H, Lq, Lk, E, _operand(q_src, qcol, cd), _operand(k_src, kcol, cd),
+                     _operand(v_src, vcol, cd), _operand(o, 0, cd))
+    if qshare is not None and not (plan.fwd == "fused" and plan.rows):
+        raise JMTError("attn_forward: qshare on an unsupported shape")
+    if plan.fwd == "small":
         # short sequences (SELF_ATTEN head, intra-modal fusion): one wave per sequence, the
         # fp32 probabilities (N*H*Lq*Lk floats) kept for the backward (small_attn.hip)
         P = torch.empty(N * H * Lq * Lk, dtype=torch.float32, device=dev)
@@ -893,11 +932,12 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
                            _ptr(v_src, vcol), (v_src.stride(0), v_src.stride(1)),
                            o.data_ptr(), (o.stride(0), o.stride(1)), scale, P)
         tensors = (q_src, k_src, v_src, P, None, None)
-    elif fused:
-        # one kernel: scores stay on chip (attn.hip); only lse is kept for the backward, which
-        # recomputes the probabilities
+    elif plan.fwd in ("short", "fused"):
+        # one kernel: scores stay on chip (attn.hip; Lq, Lk <= 32, the batch-axis attention of
+        # wo_JR and the T = 16 real-data windows: one block per sequence, attn_short.hip); only
+        # lse is kept for the backward, which recomputes the probabilities
         lse = torch.empty(N * H * Lq, dtype=torch.float32, device=dev)
-        (ops.attn_short_fwd if fused == "short" else
+        (ops.attn_short_fwd if plan.fwd == "short" else
          ops.attn_fwd_sq if qshare is not None else ops.attn_fwd)(
                      _dc(cd), N, H, Lq, Lk, dh,
                      _ptr(q_src, qcol), (q_src.stride(0), q_src.stride(1)),
@@ -915,7 +955,7 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
                  c=[o.data_ptr()], ldc=o.stride(0), sC=(o.stride(1), dh),
                  batch0=N, batch1=H, device=dev)
         tensors = (q_src, k_src, v_src, P, None, None)
-    return o, (tensors, (E, H, qcol, kcol, vcol, ldS, scale, cd, fused))
+    return o, (tensors, AttnMeta(E, H, qcol, kcol, vcol, ldS, scale, cd, plan.fwd))
 
 
 def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
@@ -923,39 +963,57 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
     sources; the same qcol/kcol/vcol column offsets; dq/dk/dv may be the same packed buffer).
     qshare: as attn_forward's.  dQ is then still written per sequence, unless merge_dq: one
     dQ = dS_i K_i + dS_j K_j per shared query in its first use's rows of dq, the second use's
-    rows left unwritten."""
+    rows left unwritten.  The path is attn_plan's answer for the buffers as they are handed in."""
+    (q_src, k_src, v_src, *_), meta = saved
+    E, H, qcol, kcol, vcol, _, _, cd, fwd = meta
+    Lq, N = q_src.shape[0], q_src.shape[1]
+    Lk = k_src.shape[0]
+    v8 = _vec(cd)
+    if go.dtype != cd or go.stride(-1) != 1 or go.stride(0) % v8 or go.stride(1) % v8:
+        go = _cast_keep_layout(go if go.stride(-1) == 1 else go.contiguous(), cd)
+    if fwd != "gemm" and not _small_aligned(go, 0, cd):
+        go = go.clone(memory_format=torch.contiguous_format)
+    # decided again with the buffers at hand and the switches as they are now
+    bwd = attn_plan(cd, N, H, Lq, Lk, E, _operand(q_src, qcol, cd), _operand(k_src, kcol, cd),
+                    _operand(v_src, vcol, cd), None, _operand(go, 0, cd), _operand(dq, qcol, cd),
+                    _operand(dk, kcol, cd), _operand(dv, vcol, cd), fwd=fwd).bwd
+    if qshare is not None and bwd != "pds_dkdv":
+        raise JMTError("attn_backward: qshare with buffers the P / dS + dK / dV / dQ kernels "
+                       f"do not take (attn_plan: {bwd})")
+    # the fused kernels' layout contract covers the gradient buffers too: a misaligned one is
+    # written through an aligned (contiguous) temporary and copied back.  Aliased buffers
+    # (packed qkv — possibly distinct view objects of one buffer) share one temporary: keyed
+    # on the memory the view spans, not on the Python object.
+    outs, tmps = [], {}
+    for buf, col in ((dq, qcol), (dk, kcol), (dv, vcol)):
+        if bwd == "gemm" or _small_aligned(buf, col, cd):
+            outs.append(buf)
+            continue
+        key = (buf.data_ptr(), tuple(buf.shape), tuple(buf.stride()))
+        if key not in tmps:
+            tmps[key] = (buf, buf.clone(memory_format=torch.contiguous_format))
+        outs.append(tmps[key][1])
+    _attn_backward_launch(bwd, saved, go, *outs, qshare, merge_dq)
+    for buf, tmp in tmps.values():
+        buf.copy_(tmp)
+
+
+def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
+    """The launches of attn_backward's path `bwd` (attn_plan) on normalised buffers."""
     (q_src, k_src, v_src, P, o, lse), meta = saved
-    E, H, qcol, kcol, vcol, ldS, scale, cd, fused = meta
+    E, H, qcol, kcol, vcol, ldS, scale, cd, _ = meta
     Lq, N = q_src.shape[0], q_src.shape[1]
     Lk = k_src.shape[0]
     dh = E // H
     dev = q_src.device
-    v8 = _vec(cd)
-    if go.dtype != cd or go.stride(-1) != 1 or go.stride(0) % v8 or go.stride(1) % v8:
-        go = _cast_keep_layout(go if go.stride(-1) == 1 else go.contiguous(), cd)
     sq_l, sq_n = q_src.stride(0), q_src.stride(1)
     sk_l, sk_n = k_src.stride(0), k_src.stride(1)
     sv_l, sv_n = v_src.stride(0), v_src.stride(1)
     so_l, so_n = go.stride(0), go.stride(1)
-    if fused and not _small_aligned(go, 0, cd):
-        go = go.clone(memory_format=torch.contiguous_format)
-        so_l, so_n = go.stride(0), go.stride(1)
-    if fused in ("small", "short"):
-        # the kernel's layout contract covers the gradient buffers too: a misaligned one is
-        # written through an aligned (contiguous) temporary and copied back.  Aliased buffers
-        # (packed qkv — possibly distinct view objects of one buffer) share one temporary: keyed
-        # on the memory the view spans, not on the Python object.
-        outs, tmps = [], {}
-        for buf, col in ((dq, qcol), (dk, kcol), (dv, vcol)):
-            if _small_aligned(buf, col, cd):
-                outs.append((buf, col))
-                continue
-            key = (buf.data_ptr(), tuple(buf.shape), tuple(buf.stride()))
-            if key not in tmps:
-                tmps[key] = (buf, buf.clone(memory_format=torch.contiguous_format))
-            outs.append((tmps[key][1], col))
-        gouts = [a for t, c in outs for a in (_ptr(t, c), (t.stride(0), t.stride(1)))]
-        if fused == "small":
+    if bwd in ("small", "short"):
+        gouts = [a for t, c in ((dq, qcol), (dk, kcol), (dv, vcol))
+                 for a in (_ptr(t, c), (t.stride(0), t.stride(1)))]
+        if bwd == "small":
             ops.small_attn_bwd(_dc(cd), N, H, Lq, Lk, E, go.data_ptr(), (so_l, so_n),
                                _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
                                _ptr(v_src, vcol), (sv_l, sv_n), P, *gouts, scale)
@@ -965,24 +1023,17 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
                                o.data_ptr(), (o.stride(0), o.stride(1)),
                                _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
                                _ptr(v_src, vcol), (sv_l, sv_n), lse, *gouts, scale)
-        for buf, tmp in tmps.values():
-            buf.copy_(tmp)
         return
-    if (fused and ops._attn_dkdv["on"] and _small_aligned(dk, kcol, cd)
-            and _small_aligned(dv, vcol, cd)
-            and ops.attn_dkdv_ok(N, H, Lq, Lk, dh, so_l, sq_l, dk.stride(0), dv.stride(0))):
+    if bwd in ("pds_dkdv", "bwd64_dkdv"):
         # P and dS (rows of 128-key tiles) -> dK = dS^T Q and dV = P^T dO in one persistent
         # kernel; with the 128-row P / dS kernel (default) dQ = dS K is that kernel's third
         # product (JMT_ATTN_PDS=0: dQ inside the 64-row backward kernel instead)
         ldp = ops.attn_dkdv_ldp(Lk)
         P = torch.empty(N * H * Lq * ldp, dtype=cd, device=dev)
         dS = torch.empty(N * H * Lq * ldp, dtype=cd, device=dev)
-        pds = ops._attn_pds["on"] and _small_aligned(dq, qcol, cd) and _small_aligned(
-            k_src, kcol, cd) and ops.attn_pds_ok(
-            Lq, Lk, dq.stride(0), max(sk_l, sv_l), H)
+        pds = bwd == "pds_dkdv"
         dq_args = (_ptr(dq, qcol), (dq.stride(0), dq.stride(1)))
         if qshare is not None:
-            assert pds, "attn_backward: qshare on an unsupported shape"
             ops.attn_bwd_sq(_dc(cd), N, H, Lq, Lk, dh, go.data_ptr(), (so_l, so_n),
                             o.data_ptr(), (o.stride(0), o.stride(1)),
                             _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
@@ -1003,10 +1054,9 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
                       (dk.stride(0), dk.stride(1)), _ptr(dv, vcol), (dv.stride(0), dv.stride(1)),
                       *((_ptr(k_src, kcol), (sk_l, sk_n)) + dq_args if pds else ()))
         return
-    assert qshare is None, "attn_backward: qshare on an unsupported shape"
     bS = (H * Lq * ldS, Lq * ldS)
     dS = torch.empty(N * H * Lq * ldS, dtype=cd, device=dev)
-    if fused:
+    if bwd == "bwd64_gemm":
         # P recomputed from lse, dP, softmax backward and dQ = dS K in one kernel; the exact P
         # and dS are written once for the dK / dV products below
         P = torch.empty(N * H * Lq * ldS, dtype=cd, device=dev)

@@ -30,8 +30,9 @@ import torch
 from torch.autograd import Function
 
 from . import ops, streams
-from .functional import (_dc, _grad_buffer, _grad_done, _ptr, attn_backward, attn_forward,
-                         attn_shared_ok, compute_dtype, weight_as, wgrad_defer_ok, wgrad_scope)
+from .functional import (AttnOperand, _dc, _grad_buffer, _grad_done, _operand, _ptr,
+                         attn_backward, attn_forward, attn_plan, compute_dtype, weight_as,
+                         wgrad_defer_ok, wgrad_scope)
 
 _enabled = {"on": os.environ.get("JMT_GROUPED", "1") != "0"}
 # the cross-attention backward's three stream-gradient GEMMs on branch streams: measured
@@ -695,8 +696,13 @@ class CrossAttention6Fn(Function):
         in_b = [M[m][1] for m, _, _ in pairs]
         sf = QKV.view(NP * B, T, 3 * E).permute(1, 0, 2)
         qtab = shared_query_table(pairs) if _shared_q["on"] else None
-        if qtab is not None and not attn_shared_ok(sf, sf, sf, E, H, 0, E, 2 * E):
-            qtab = None
+        if qtab is not None:
+            # the backward's buffers as this node builds them: dQKV laid out like QKV, dO
+            # batch-major (NP * B, T, E) with row stride E
+            oq, ok, ov = (_operand(sf, c, cd) for c in (0, E, 2 * E))
+            od = AttnOperand(True, E)
+            if not attn_plan(cd, NP * B, H, T, T, E, oq, ok, ov, od, od, oq, ok, ov).shared_q:
+                qtab = None
         # queries and packed key/values, one launch each.  Shared queries: the projection of the
         # first use only (the q columns of the other uses' rows of QKV stay unused); otherwise
         # each module's query projection is evaluated for both of its calls, as the reference does

@@ -533,14 +533,16 @@ _attn_dkdv = {"on": os.environ.get("JMT_ATTN_DKDV", "1") != "0"}
 _attn_pds = {"on": os.environ.get("JMT_ATTN_PDS", "1") != "0"}
 
 
-def attn_pds_ok(Lq, Lk, sdq_l, sk_l, H) -> bool:
-    """Host-side mirror of the dq = NULL checks of jmt_attn_bwd and the dQ checks of
-    jmt_attn_dkdv: P / dS rows of attn_dkdv_ldp(Lk) with 32-bit offsets over Lq + 128 rows, a
-    128-row dQ tile and Lk K rows within 32-bit byte offsets."""
-    ldp = attn_dkdv_ldp(Lk)
-    lim = 1 << 31
-    return ((Lq + 128) * ldp * 2 < lim // 2 and sdq_l >= H * 512 and 128 * sdq_l * 2 < lim
-            and Lk * sk_l * 2 < lim)
+def attn_fwd_rows_ok(N, H, Lq, Lk, sk_l, sv_l) -> bool:
+    """jmt_attn_fwd takes the whole-row kernel for these sizes and K / V row strides, so
+    attn_fwd_sq accepts them (jmt_attn_fwd_rows_ok; the forward-rows switch included)."""
+    return bool(_lib.load().jmt_attn_fwd_rows_ok(N, H, Lq, Lk, sk_l, sv_l))
+
+
+def attn_bwd_pds_ok(N, H, Lq, Lk, ldp, sk_l, sv_l) -> bool:
+    """attn_bwd with dq_ptr None (the 128-row P / dS kernel) takes these sizes and row strides
+    (jmt_attn_bwd_pds_ok)."""
+    return bool(_lib.load().jmt_attn_bwd_pds_ok(N, H, Lq, Lk, ldp, sk_l, sv_l))
 
 
 def attn_dkdv_ldp(Lk: int) -> int:
@@ -548,16 +550,11 @@ def attn_dkdv_ldp(Lk: int) -> int:
     return (Lk + 127) // 128 * 128
 
 
-def attn_dkdv_ok(N, H, Lq, Lk, dh, sgo_l, sq_l, sdk_l, sdv_l) -> bool:
-    """Host-side mirror of jmt_attn_dkdv's range checks (csrc/attn_dkdv.hip): 512-wide heads,
-    32-bit row offsets of dO / Q / P (Lq rows < 2 GiB) and of a 128-row dK / dV tile, and the
-    item count.  The caller takes the batched-GEMM dK / dV path when this says no."""
-    ldp = attn_dkdv_ldp(Lk)
-    lim = 1 << 31
-    return (dh == 512 and sdk_l >= H * dh and sdv_l >= H * dh
-            and 128 * sdk_l * 2 < lim and 128 * sdv_l * 2 < lim
-            and N * H * 2 * (ldp // 128) < lim
-            and Lq * sgo_l * 2 < lim and Lq * sq_l * 2 < lim and Lq * ldp * 2 < lim)
+def attn_dkdv_ok(N, H, Lq, Lk, ldp, sgo_l, sq_l, sdk_l, sdv_l, sk_l=0, sdq_l=None) -> bool:
+    """attn_dkdv takes these sizes and row strides (jmt_attn_dkdv_ok); sdq_l (with sk_l): the
+    launch with dQ."""
+    return bool(_lib.load().jmt_attn_dkdv_ok(N, H, Lq, Lk, ldp, sgo_l, sq_l, sk_l, sdk_l, sdv_l,
+                                             sdq_l or 0, int(sdq_l is not None)))
 
 
 def attn_dkdv(dtype, N, H, Lq, Lk, dh, p, ds, ldp, go_ptr, sgo, q_ptr, sq, dk_ptr, sdk, dv_ptr,
@@ -631,16 +628,6 @@ def attn_dkdv_sq(dtype, N, H, Lq, Lk, dh, p, ds, ldp, go_ptr, sgo, q_ptr, sq, dk
              "bytes": float(N * H) * ((2 * Lq + 2 * Lk) * dh * es +
                                       2 * Lq * attn_dkdv_ldp(Lk) * es + extra) -
                       float((N - nq) * H) * Lq * dh * es}, launch)
-
-
-def attn_sq_ok(dtype, dh, Lq, Lk, sk_l, sv_l) -> bool:
-    """Host-side mirror of what the *_sq entry points take: the 16-bit fused kernels, the
-    whole-row forward (Lq > 64, Lk K / V rows within 32-bit byte offsets) and the P / dS +
-    dK / dV / dQ pair of kernels switched on."""
-    lim = 1 << 31
-    return (dtype != F32 and attn_supported(dtype, dh) and _attn_dkdv["on"] and _attn_pds["on"]
-            and os.environ.get("JMT_ATTN_FWD_ROWS", "1") != "0"
-            and Lq > 64 and Lk * sk_l * 2 < lim and Lk * sv_l * 2 < lim)
 
 
 def attn_short_ok(dtype: int, dh: int, Lq: int, Lk: int) -> bool:

@@ -837,8 +837,9 @@ def test_attention_backward_dkdv_out_of_range_stride_takes_gemm_path():
     cd = torch.bfloat16
     E, H, N, Lq, Lk = 512, 1, 1, 70, 129
     sl = (1 << 23) + 1024                       # 128 * sl * 2 B > 2 GiB
-    assert not ops.attn_dkdv_ok(N, H, Lq, Lk, E, 3 * E, 3 * E, sl, sl)
-    assert ops.attn_dkdv_ok(N, H, Lq, Lk, E, 3 * E, 3 * E, 2 * E, 2 * E)
+    ldp = ops.attn_dkdv_ldp(Lk)
+    assert not ops.attn_dkdv_ok(N, H, Lq, Lk, ldp, 3 * E, 3 * E, sl, sl)
+    assert ops.attn_dkdv_ok(N, H, Lq, Lk, ldp, 3 * E, 3 * E, 2 * E, 2 * E)
     g = torch.Generator(device=DEV).manual_seed(33)
     qkv = torch.randn(N, Lq, 3 * E, device=DEV, generator=g).to(cd).permute(1, 0, 2)
     kv = torch.randn(N, Lk, 2 * E, device=DEV, generator=g).to(cd).permute(1, 0, 2)

@@ -137,3 +137,71 @@ def test_bench_synthetic_batches_identical_across_world_sizes():
         assert torch.equal(one[k], torch.cat([two[0][k], two[1][k]], 0))
     for k in range(2, 4):                                 # labels (1, B*T)
         assert torch.equal(one[k].view(6, 5), torch.cat([t[k].view(3, 5) for t in two], 0))
+
+
+def test_attn_plan_table():
+    """functional.attn_plan (no GPU, no tensors): one row per forward path, per backward path,
+    per reason to leave the default backward and per switch; the shared-query answer for the
+    CrossAttention6 layout.  Operands as (aligned, row stride): q / dq in a packed (L, N, 3E)
+    buffer, k / v / dk / dv in a packed (L, N, 2E) one, o / dO (L, N, E)."""
+    from jmt import _lib, ops
+    from jmt.functional import AttnOperand as Op, AttnPlan, attn_plan
+    bf, f32, E = torch.bfloat16, torch.float32, 512
+    lib = _lib.load()
+
+    def plan(cd, Lq, Lk, N, fwd=None, grads=True, **kw):
+        d = dict(q=Op(True, 3 * E), k=Op(True, 2 * E), v=Op(True, 2 * E), o=Op(True, E))
+        if grads:
+            d.update(go=Op(True, E), dq=Op(True, 3 * E), dk=Op(True, 2 * E), dv=Op(True, 2 * E))
+        d.update(kw)
+        return attn_plan(cd, N, 1, Lq, Lk, E, fwd=fwd, **d)
+
+    sl = (1 << 23) + 1024                      # 128 rows x sl x 2 B > 2 GiB
+    assert plan(bf, 6, 6, 3) == AttnPlan("small", False, "small", False)
+    assert plan(bf, 20, 32, 2) == AttnPlan("short", False, "short", False)
+    assert plan(bf, 64, 64, 1) == AttnPlan("fused", False, "pds_dkdv", False)
+    assert plan(bf, 65, 33, 2) == AttnPlan("fused", True, "pds_dkdv", True)
+    assert plan(bf, 65, 33, 2, grads=False) == AttnPlan("fused", True, None, False)
+    assert plan(f32, 6, 6, 3) == AttnPlan("small", False, "small", False)
+    # reasons to leave the default backward
+    assert plan(bf, 65, 33, 2, dq=Op(False, 3 * E)) == AttnPlan("fused", True, "bwd64_dkdv", False)
+    assert plan(bf, 65, 33, 2, k=Op(False, 2 * E)) == AttnPlan("fused", True, "bwd64_dkdv", False)
+    assert plan(bf, 65, 33, 2, dk=Op(False, 2 * E)) == AttnPlan("fused", True, "bwd64_gemm", False)
+    assert plan(bf, 70, 129, 1, dk=Op(True, sl), dv=Op(True, sl)) == \
+        AttnPlan("fused", True, "bwd64_gemm", False)
+    # (Lq + 128) x ldp 16-bit values reach 1 GiB: no P / dS kernel; at Lq = 32768 the Lq rows
+    # of P reach 2 GiB as well: no attn_dkdv either
+    assert plan(bf, 16384, 32768, 1) == AttnPlan("fused", True, "bwd64_dkdv", False)
+    assert plan(bf, 32768, 32768, 1) == AttnPlan("fused", True, "bwd64_gemm", False)
+    assert plan(f32, 65, 33, 2) == AttnPlan("gemm", False, "gemm", False)
+    # a misaligned source leaves the small / short kernels
+    assert plan(bf, 6, 6, 3, q=Op(False, 3 * E)).fwd == "fused"
+    assert plan(bf, 20, 32, 2, v=Op(False, 2 * E)).fwd == "fused"
+    # the switches, read at every call
+    for sw, args, want in (
+            (ops._attn_fused, (bf, 65, 33, 2), AttnPlan("gemm", False, "gemm", False)),
+            (ops._attn_fused, (bf, 6, 6, 3), AttnPlan("gemm", False, "gemm", False)),
+            (ops._attn_short, (bf, 20, 32, 2), AttnPlan("fused", False, "pds_dkdv", False)),
+            (ops._attn_dkdv, (bf, 65, 33, 2), AttnPlan("fused", True, "bwd64_gemm", False)),
+            (ops._attn_pds, (bf, 65, 33, 2), AttnPlan("fused", True, "bwd64_dkdv", False))):
+        sw["on"] = False
+        try:
+            assert plan(*args) == want, (args, plan(*args))
+            # the backward of a forward that ran fused stays on the fused kernels' state
+            if sw is ops._attn_fused:
+                assert plan(*args, fwd="fused").bwd == "pds_dkdv"
+        finally:
+            sw["on"] = True
+    lib.jmt_attn_set_fwd_rows(0)
+    try:
+        assert plan(bf, 65, 33, 2) == AttnPlan("fused", False, "pds_dkdv", False)
+    finally:
+        lib.jmt_attn_set_fwd_rows(-1)
+    assert plan(bf, 65, 33, 2) == AttnPlan("fused", True, "pds_dkdv", True)
+    # CrossAttention6 (B = 1): six sequences of T rows in one packed (6, T, 3E) buffer, dQKV laid
+    # out like it, dO batch-major with row stride E
+    for T, want in ((65, True), (64, False)):
+        q, k, v = (Op(True, 3 * E),) * 3
+        od = Op(True, E)
+        p = attn_plan(bf, 6, 1, T, T, E, q, k, v, od, od, q, k, v)
+        assert (p.fwd, p.bwd, p.shared_q) == ("fused", "pds_dkdv", want)
