@@ -1,5 +1,7 @@
 // Persistent form of the GEMM (jmt_gemm cfg 40): one block per CU walks whole output
 // tiles with one continuous LDS-DMA pipeline (details at gemm_persist_kernel).
+#include <type_traits>
+
 #include "gemm_tile.h"
 
 namespace jmt {
@@ -41,13 +43,19 @@ struct PItem {
   int sp, kt0, len;             // split-K: split index, its first K-tile (64 deep) and count
 };
 
-// work item w (block w % G, G a multiple of 8: the hardware deals blocks to the XCDs round-robin)
-// -> a logical tile, bijectively: the items of one XCD are a contiguous range of logical tiles
-// (n fastest), so the N tiles of one A row panel run at the same time on one XCD's L2.
+// work item w of W (block w % G, G a multiple of 8: the hardware deals blocks to the XCDs
+// round-robin) -> a logical item, bijectively: the items of one XCD (w & 7) are a contiguous range
+// of logical items
+__device__ __forceinline__ int xcd_slot(int w, int W) {
+  const int x = w & 7, q = W >> 3, r = W & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (w >> 3);
+}
+
+// work item w -> a logical tile (n fastest), so the N tiles of one A row panel run at the same
+// time on one XCD's L2.
 __device__ __forceinline__ PItem pitem(const GemmParams& p, int w, int W) {
   const int ntile = p.tiles_m * p.tiles_n;
-  const int x = w & 7, q = W >> 3, r = W & 7;
-  const int L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (w >> 3);
+  const int L = xcd_slot(w, W);
   const int b = L / ntile, t = L - b * ntile;
   PItem it;
   it.m0 = (t / p.tiles_n) * 256;
@@ -68,8 +76,7 @@ struct PWalk {
 };
 __device__ __forceinline__ PWalk pwalk_init(const GemmParams& p, int w, int W, int G) {
   const int ntile = p.tiles_m * p.tiles_n;
-  const int x = w & 7, q = W >> 3, r = W & 7;
-  const int L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (w >> 3);
+  const int L = xcd_slot(w, W);
   const int bs = L / ntile, t = L - bs * ntile;
   const int b = bs / p.splits;
   PWalk s;
@@ -821,293 +828,131 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmParams p) {
 constexpr int P2_D = 10;
 static_assert(P2_D % 2 == 0 && P2_D <= 10, "pp2 deadline counts are derived for an even P2_D <= 10");
 
+// One schedule (pp2_run), two item sources.  The schedule owns the phases, the DMA stream, the
+// deadline counts, the accumulators and the order of everything; a source (Src) only says where
+// the block's items and their operands come from and what an item's epilogue stores:
+//   Item / Cursor, first() / next() / item()   the block's items w, w + G, w + 2 G, ...
+//   ktiles(nm)                                 the K-tiles of all of them (the stream's length)
+//   operand<ISA, KM>()                         the stream's operand (ld, K steps, K-concat segment):
+//                                              the launch's, or zeros where it follows the item
+//   stream<ISA, KM>(item, k0, operand)         that operand at K offset k0 of an item: the tile's
+//                                              base, the K-tiles left in its K-concat segment and
+//                                              (CLAMP) the last row a lane may read; a source
+//                                              whose operand follows the item sets it here
+//   epo()                                      the VMEM operations the deadlines count per epilogue
+//   epilogue(item, acc, rsum, smem, ...)       the item's stores
+// GemmSrc walks one GemmParams problem (cfg 45, and cfg 44 with SPL); GroupSrc walks the items of
+// several weight-gradient problems (jmt_gemm_grouped).  The vmcnt rule at the head of this file
+// holds for any source whose epilogue issues AT LEAST epo() VMEM operations for every item,
+// whatever the item: vmcnt counts in issue order, so operations the count leaves out (GroupSrc's
+// beta * C and d[m] loads, or all of them under dbg 32) only make a deadline wait for more.
+struct PPOperand {
+  int64_t ld, dk, hk;           // leading dimension; bytes per K-tile and per k-half
+  int seg;                      // K-tiles per K-concat segment
+  template <typename T, bool KM>
+  __device__ __forceinline__ static PPOperand make(int64_t ld, int mode, int kseg) {
+    const int64_t dk = (KM ? (int64_t)64 : (int64_t)64 * ld) * (int64_t)sizeof(T);
+    return {ld, dk, dk / 2, mode >= 2 ? kseg / 64 : 1 << 30};
+  }
+};
+struct PPStream {
+  const char* base;             // row 0, K offset k0 of the operand's 256-row tile
+  int left;                     // K-tiles from k0 to the end of its K-concat segment
+  int rmax;                     // CLAMP: the tile's last readable row (or 8-row chunk, MN-major)
+};
+
 // SPL: 0 the 16-bit C epilogue (persist_epilogue, EPI), 1 split-K fp32 slabs (pp_slab_epilogue),
 // 2 slabs + the A row sums (dbias_ws)
-template <typename T, bool AK, bool BK, int EPI, int GRP, int SPL = 0>
-__device__ __forceinline__ void pp2_run(const GemmParams& p, uint32_t lbase, const char* smem,
-                                        const float* bias_lds, int nm, int W) {
+template <typename T, int EPI, int SPL>
+struct GemmSrc {
   using C = CfgPP;
-  typedef typename Frag16<T>::t F;
-  constexpr bool ISA = GRP == 1;                           // this group's operand: A (else B)
-  constexpr bool KM = ISA ? AK : BK;
-  constexpr int NST = SPL ? C::TM * C::TN + (SPL == 2 ? 2 : 0) : C::TM * (C::TN / 2);
-  constexpr int NLD = SPL ? 0 : ((EPI & 1) ? C::TM * C::TN : 0) + ((EPI & 2) ? C::TM * C::TN : 0);
-  constexpr int EPO = NST + NLD;                           // VMEM operations of one epilogue
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wl = wid & 3;
-  constexpr int wm = GRP;
-  const int wn = wl;
-  const int G = gridDim.x;
-  // K-tiles of this block's items (split-K items differ by one K-tile at most)
-  int nT = nm * (p.K >> 6);
-  if (SPL && p.splits > 1) {
-    PWalk w = pwalk_init(p, blockIdx.x, W, G);
-    nT = 0;
-    for (int k = 0; k < nm; ++k) {
-      if (k) pwalk_next(p, w);
-      nT += pwalk_item(p, w).len;
-    }
-  }
-  const int nh = 2 * nT;                                   // k-halves of the block's stream
-  const int64_t ld = ISA ? p.lda : p.ldb;
-  // per-lane byte offsets of this wave's instructions 2 wl, 2 wl + 1 of each half (h) of its
-  // operand's k-half image, relative to the operand's K-tile base
-  // (the A rows of a last, partial row panel (M % 256 != 0) are clamped to the last row — or the
-  // last 8-row chunk, MN-major — in set_stream; their products are never stored)
-  int rowv[2][2], kkv[2][2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-      chunk_src<T, KM, 64, 256>((8 * h + 2 * wl + e) * 64 + lane, rowv[h][e], kkv[h][e]);
-  const int64_t dk = (KM ? (int64_t)64 : (int64_t)64 * ld) * (int64_t)sizeof(T);   // K-tile
-  const int64_t hk = dk / 2;                                                          // k-half
-  const int seg = (ISA ? p.a_mode : p.b_mode) >= 2 ? (ISA ? p.a_kseg : p.b_kseg) / 64 : 1 << 30;
+  using Item = PItem;
+  using Cursor = PWalk;
+  // the A rows of a last, partial row panel (cfg 45, M % 256 != 0) are clamped to the last row;
+  // their products are never stored
+  static constexpr bool CLAMP = true;
+  static constexpr int NST = SPL ? C::TM * C::TN + (SPL == 2 ? 2 : 0) : C::TM * (C::TN / 2);
+  static constexpr int NLD =
+      SPL ? 0 : ((EPI & 1) ? C::TM * C::TN : 0) + ((EPI & 2) ? C::TM * C::TN : 0);
+  const GemmParams& p;
+  int W;
 
-  PWalk iss_w = pwalk_init(p, blockIdx.x, W, G);
-  PItem iss_it = pwalk_item(p, iss_w);
-  int iss_k = 0, iss_kt = 0, left = 0;
-  const char* ps[2][2];
-  auto set_stream = [&]() {
-    const int k0 = (iss_it.kt0 + iss_kt) * 64;
+  __device__ __forceinline__ Cursor first() const {
+    return pwalk_init(p, blockIdx.x, W, gridDim.x);
+  }
+  __device__ __forceinline__ void next(Cursor& c) const { pwalk_next(p, c); }
+  __device__ __forceinline__ Item item(const Cursor& c) const { return pwalk_item(p, c); }
+  // (split-K items differ by one K-tile at most)
+  __device__ __forceinline__ int ktiles(int nm) const {
+    int nT = nm * (p.K >> 6);
+    if (SPL && p.splits > 1) {
+      Cursor c = first();
+      nT = 0;
+      for (int k = 0; k < nm; ++k) {
+        if (k) next(c);
+        nT += item(c).len;
+      }
+    }
+    return nT;
+  }
+  template <bool ISA, bool KM>
+  __device__ __forceinline__ PPOperand operand() const {   // wave-constant
+    return ISA ? PPOperand::make<T, KM>(p.lda, p.a_mode, p.a_kseg)
+               : PPOperand::make<T, KM>(p.ldb, p.b_mode, p.b_kseg);
+  }
+  template <bool ISA, bool KM>
+  __device__ __forceinline__ PPStream stream(const Item& it, int k0, const PPOperand& o) const {
     int kl;
-    const T* X = ISA ? operand_base<T>(p.a_ptr, p.a_mode, p.sA0, p.sA1, iss_it.b0, iss_it.b1,
-                                       p.a_kseg, k0, kl)
-                     : operand_base<T>(p.b_ptr, p.b_mode, p.sB0, p.sB1, iss_it.b0, iss_it.b1,
-                                       p.b_kseg, k0, kl);
-    const int r0 = ISA ? iss_it.m0 : iss_it.n0;
-    const char* sx = (const char*)(KM ? X + (int64_t)r0 * ld + kl : X + (int64_t)kl * ld + r0);
-    const int rmax = ISA ? p.M - (KM ? 1 : 8) - r0 : 256;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int r = min(rowv[h][e], rmax);
-        ps[h][e] = sx + (KM ? (int64_t)r * ld + kkv[h][e] : (int64_t)kkv[h][e] * ld + r) *
-                            (int64_t)sizeof(T);
-      }
-    left = seg - (kl >> 6);
-  };
-  auto next_ktile = [&]() {
-    if (++iss_kt == iss_it.len) {
-      iss_kt = 0;
-      if (++iss_k < nm) {
-        pwalk_next(p, iss_w);
-        iss_it = pwalk_item(p, iss_w);
-        set_stream();
-      }
-    } else if (--left == 0) {
-      set_stream();
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int e = 0; e < 2; ++e) ps[h][e] += dk;
-    }
-  };
-  // this wave's 4 instructions of k-half g (its operand's two halves) from the current K-tile
-  auto issue = [&](int g) {
-    const uint32_t dst = lbase + (g & 3) * PP_SLOT + (ISA ? 0 : 16384) + 2 * wl * 1024;
-    const int64_t kh = (g & 1) ? hk : 0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) glds16_at(ps[h][e] + kh, dst + (8 * h + e) * 1024);
-  };
-  // epilogues issued in this phase's / the previous phase's load segment (deadline counts)
-  bool ep_cur = false, ep_prev = false;
-  // k-half g retired by this wave (at phase g - 1); counts as in the header comment, rounded
-  // down near the stream's end
-  auto deadline = [&](int g) {
-    if (g >= nh) return;
-    const int m = g - 1;
-    if constexpr (GRP == 0) {
-      // younger: its piece of k-half m + 2 (phase m) and phase m's epilogue
-      const int n = (m + 2 < nh ? 4 : 0) + (ep_cur ? EPO : 0);
-      if (n == 4) wait_vmcnt<4>();
-      else wait_vm_le(n);
-    } else {
-      // younger: its pieces of k-halves m + 2 (phase m - 1) and m + 3 (phase m)
-      const int n = (m + 2 < nh ? 4 : 0) + (m + 3 < nh ? 4 : 0) +
-                    ((ep_prev ? 1 : 0) + (ep_cur ? 1 : 0)) * EPO;
-      if (n == 8) wait_vmcnt<8>();
-      else wait_vm_le(n);
-    }
-  };
-
-  // prologue: group 0 the B halves of k-halves 0, 1; group 1 the A halves of 0, 1, 2
-  set_stream();
-  if constexpr (GRP == 0) {
-    issue(0);
-    issue(1);
-    wait_vmcnt<4>();                                       // k-half 0 retired
-  } else {
-    issue(0);
-    if (nh > 1) issue(1);
-    if (nh > 2) {
-      next_ktile();
-      issue(2);
-    }
-    wait_vm_le((nh > 1 ? 4 : 0) + (nh > 2 ? 4 : 0));
+    const T* X = ISA ? operand_base<T>(p.a_ptr, p.a_mode, p.sA0, p.sA1, it.b0, it.b1, p.a_kseg,
+                                       k0, kl)
+                     : operand_base<T>(p.b_ptr, p.b_mode, p.sB0, p.sB1, it.b0, it.b1, p.b_kseg,
+                                       k0, kl);
+    const int r0 = ISA ? it.m0 : it.n0;
+    PPStream s;
+    s.base = (const char*)(KM ? X + (int64_t)r0 * o.ld + kl : X + (int64_t)kl * o.ld + r0);
+    s.left = o.seg - (kl >> 6);
+    s.rmax = ISA ? p.M - (KM ? 1 : 8) - r0 : 256;
+    return s;
   }
-  __builtin_amdgcn_s_barrier();
-  if constexpr (GRP == 1) __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-
-  f32x4 acc[C::TM][C::TN];
-#pragma unroll
-  for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-    for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  F fa[8] = {}, fb[4] = {};
-  PWalk cur_w = pwalk_init(p, blockIdx.x, W, G);
-  PItem cur = pwalk_item(p, cur_w);
-  int cur_left = cur.len;
-  float rsum[2] = {0.f, 0.f};                              // SPL 2: row sums of sub-tiles wn, wn + 4
-  auto epilogue = [&]() {
+  __device__ __forceinline__ int epo() const { return NST + NLD; }
+  __device__ __forceinline__ void epilogue(const Item& it, f32x4 (&acc)[C::TM][C::TN],
+                                           float (&rsum)[2], const char* smem, int lane, int wm,
+                                           int wn) const {
     if constexpr (SPL) {
-      pp_slab_epilogue<C, 0, 8>(p, cur, acc, lane, wm, wn);
+      pp_slab_epilogue<C, 0, 8>(p, it, acc, lane, wm, wn);
       if constexpr (SPL == 2) {
-        pp_rowsum_store(p, cur, rsum[0], wm * C::WTM + 16 * wn, lane);
-        pp_rowsum_store(p, cur, rsum[1], wm * C::WTM + 64 + 16 * wn, lane);
+        pp_rowsum_store(p, it, rsum[0], wm * C::WTM + 16 * wn, lane);
+        pp_rowsum_store(p, it, rsum[1], wm * C::WTM + 64 + 16 * wn, lane);
         rsum[0] = rsum[1] = 0.f;
       }
     } else {
-      persist_epilogue<T, C, EPI>(p, cur, acc, bias_lds, lane, wm, wn, false,
-                                  cur.m0 + 256 > p.M);
-    }
-  };
-  for (int t = 0; t < nT; ++t) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int m = 2 * t + ks;
-      // ---- load segment
-      ep_prev = ep_cur;
-      ep_cur = false;
-      if (ks == 0) {
-        if (cur_left == 0) {                               // previous item done: its epilogue
-          epilogue();
-          ep_cur = true;
-#pragma unroll
-          for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-            for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-          pwalk_next(p, cur_w);
-          cur = pwalk_item(p, cur_w);
-          cur_left = cur.len;
-        }
-        --cur_left;
-      }
-      // stream step: group 0 issues k-half m + 2 (K-tile t + 1), group 1 k-half m + 3
-      if ((GRP == 0 && ks == 0) || (GRP == 1 && ks == 1)) next_ktile();
-      const char* slot = smem + (m & 3) * PP_SLOT;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        fb[j] = read_frag16<T, BK, 64, 256>(slot + 16384, wn * C::WTN + 16 * j, 0);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        fa[i] = read_frag16<T, AK, 64, 256>(slot, wm * C::WTM + 16 * i, 0);
-      {
-        const int g = m + (GRP == 0 ? 2 : 3);
-        if (g < nh) issue(g);
-      }
-      if constexpr (GRP == 1) deadline(m + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- MFMA segment
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(fb[j], fa[i], acc[i][j]);
-      __builtin_amdgcn_s_setprio(0);
-      if constexpr (SPL == 2) {                            // A row sums, sub-tiles wn and wn + 4
-        if (wn == 0) { rsum[0] = rowsum8(fa[0], rsum[0]); rsum[1] = rowsum8(fa[4], rsum[1]); }
-        else if (wn == 1) { rsum[0] = rowsum8(fa[1], rsum[0]); rsum[1] = rowsum8(fa[5], rsum[1]); }
-        else if (wn == 2) { rsum[0] = rowsum8(fa[2], rsum[0]); rsum[1] = rowsum8(fa[6], rsum[1]); }
-        else { rsum[0] = rowsum8(fa[3], rsum[0]); rsum[1] = rowsum8(fa[7], rsum[1]); }
-      }
-      if constexpr (GRP == 0) deadline(m + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
+      // (the bias tables the kernel staged behind the slot ring)
+      const float* bias_lds = (const float*)(smem + PP_NSLOT * PP_SLOT);
+      persist_epilogue<T, C, EPI>(p, it, acc, bias_lds, lane, wm, wn, false, it.m0 + 256 > p.M);
     }
   }
-  if constexpr (GRP == 0) __builtin_amdgcn_s_barrier();
-  epilogue();
-}
+};
 
-template <typename T, bool AK, bool BK, int EPI>
-__global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* bias_lds = (float*)(smem + PP_NSLOT * PP_SLOT);
-  const int W = p.tiles_m * p.tiles_n * p.batch0 * p.batch1;
-  const int G = gridDim.x;
-  const int nm = (W - (int)blockIdx.x + G - 1) / G;
-  if (p.bias_mode == 1) {
-    const int nb = (p.n_bias > 0 ? p.batch0 : 1) * p.N;
-    for (int i = threadIdx.x; i < nb; i += 512) {
-      const int b = i / p.N;
-      bias_lds[i] = (p.n_bias > 0 ? p.bias_tab[b] : p.bias)[i - b * p.N];
-    }
-  }
-  __syncthreads();
-  if (nm <= 0 || p.K < 64) return;
-  const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  if ((threadIdx.x >> 6) < 4) pp2_run<T, AK, BK, EPI, 0>(p, lbase, smem, bias_lds, nm, W);
-  else pp2_run<T, AK, BK, EPI, 1>(p, lbase, smem, bias_lds, nm, W);
-}
-
-// split-K form (cfg 44, on the cfg 45 schedule): items are (tile, split) — the weight-gradient GEMMs (M, N = features,
-// K = B x T rows: a few 256 x 256 tiles over a long K); fp32 partial slabs (+ the A row sums) for
-// splitk_reduce_kernel, which jmt_gemm launches next
-// (An in-launch reduction — the S blocks of a tile meeting at a per-tile counter, then each
-// reducing its 256 / S rows over all S slabs — measured slower than the separate
-// splitk_reduce_kernel launch on every weight-gradient shape, 5-10 %: the reduce loop of one
-// 8-wave block per CU keeps too few slab loads in flight; profiles/r05/tn_fused_reduce_ab.txt.)
-
-template <typename T, bool AK, bool BK, int SPL>
-__global__ __launch_bounds__(512) void gemm_pp_split_kernel(GemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int W = p.tiles_m * p.tiles_n * p.batch0 * p.batch1 * p.splits;
-  const int G = gridDim.x;
-  const int nm = (W - (int)blockIdx.x + G - 1) / G;
-  if (nm <= 0 || p.K < 64) return;
-  const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  if ((threadIdx.x >> 6) < 4) pp2_run<T, AK, BK, 0, 0, SPL>(p, lbase, smem, nullptr, nm, W);
-  else pp2_run<T, AK, BK, 0, 1, SPL>(p, lbase, smem, nullptr, nm, W);
-}
-
-// ------------------------------------------------------------------ grouped split-K ping-pong
-// jmt_gemm_grouped: the split-K ping-pong schedule above (pp2_run: phases, DMA stream, deadline
-// counts unchanged) over the items of SEVERAL weight-gradient problems.  What changes is where an
-// item's operands come from: logical item L of the launch belongs to the problem p with
-// prob[p].item0 <= L < prob[p + 1].item0; within a problem the order is pwalk's (tile fastest,
-// then split, then batch entry), so the tiles of one (batch, split) are consecutive and land on
-// one XCD.  The problem's record (GroupProb, in the kernel arguments) is read with scalar loads
-// when a cursor moves to its next item.
+// jmt_gemm_grouped: logical item L of the launch belongs to the problem p with prob[p].item0 <=
+// L < prob[p + 1].item0; within a problem the order is pwalk's (tile fastest, then split, then
+// batch entry), so the tiles of one (batch, split) are consecutive and land on one XCD.  The
+// problem's record (GroupProb, in the kernel arguments) is read with scalar loads when a cursor
+// moves to its next item, so ld and the K-concat segment follow the stream's current problem.
 //
-// The vmcnt counting rule at the head of this file holds across a problem switch because the
-// epilogue's VMEM count per item does not depend on the problem: every item issues TM * TN 16-B
-// stores (+ 2 row-sum stores when any problem of the launch takes row sums: problems without
+// The epilogue's VMEM count per item does not depend on the problem: every item issues TM * TN
+// 16-B stores (+ 2 row-sum stores when any problem of the launch takes row sums: problems without
 // dbias store theirs into their own partial area, which nobody reads), whether they go to a slab
-// or, for a problem with splits == 1, straight to C.  The beta * C loads of that direct form are
-// extra operations the deadline counts do not include: an undercount only waits for more.
+// or, for a problem with splits == 1, straight to C.
 // A one-split problem with a dbias table finishes its row sums here as well: the item of column
 // panel 0 stores (dbias_acc ? d[m] : 0) + r into dbias_tab[b0][m] (rowsum_store's form in
 // gemm.hip; one writer per d[m], no atomics), its other items keep issuing their two stores into
-// the problem's partial area, so the store count per item stays uniform.  The owner's read of
-// d[m] is one more uncounted load, like the beta * C loads.
+// the problem's partial area, so the store count per item stays uniform.
 struct GItem {
   int pi, m0, n0, b0, sp, kt0, len;
 };
 
 __device__ __forceinline__ GItem gitem(const GroupParams& g, int w) {
-  const int W = g.W;
-  const int x = w & 7, q = W >> 3, r = W & 7;
-  const int L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (w >> 3);
+  const int L = xcd_slot(w, g.W);
   int pi = 0;
   for (int i = 1; i < g.nprob; ++i) pi = L >= g.prob[i].item0 ? i : pi;
   pi = __builtin_amdgcn_readfirstlane(pi);
@@ -1129,127 +974,49 @@ __device__ __forceinline__ GItem gitem(const GroupParams& g, int w) {
 }
 
 // SPL: 1 fp32 slabs (direct C where splits == 1), 2 + the A row sums
-template <typename T, bool AK, bool BK, int GRP, int SPL>
-__device__ __forceinline__ void ppg_run(const GroupParams& g, uint32_t lbase, const char* smem,
-                                        int nm) {
+template <typename T, int SPL>
+struct GroupSrc {
   using C = CfgPP;
-  typedef typename Frag16<T>::t F;
-  constexpr bool ISA = GRP == 1;                           // this group's operand: A (else B)
-  constexpr bool KM = ISA ? AK : BK;
-  constexpr int EPO = C::TM * C::TN + (SPL == 2 ? 2 : 0);  // VMEM operations of one epilogue
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wl = wid & 3;
-  constexpr int wm = GRP;
-  const int wn = wl;
-  const int G = gridDim.x;
-  int nT = 0;                                              // K-tiles of this block's items
-  for (int k = 0; k < nm; ++k) nT += gitem(g, blockIdx.x + k * G).len;
-  const int nh = 2 * nT;
-  int rowv[2][2], kkv[2][2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-      chunk_src<T, KM, 64, 256>((8 * h + 2 * wl + e) * 64 + lane, rowv[h][e], kkv[h][e]);
+  using Item = GItem;
+  using Cursor = int;                                      // the item's index w in the launch
+  static constexpr bool CLAMP = false;                     // whole tiles only: no v_min per lane
+  const GroupParams& g;
 
-  // the issue stream; dk / hk / left follow its current problem
-  GItem iss_it = gitem(g, blockIdx.x);
-  int iss_k = 0, iss_kt = 0, left = 0;
-  int64_t dk = 0, hk = 0;
-  const char* ps[2][2];
-  auto set_stream = [&]() {
-    const GroupProb& P = g.prob[iss_it.pi];
-    const int64_t ld = ISA ? P.lda : P.ldb;
+  __device__ __forceinline__ Cursor first() const { return blockIdx.x; }
+  __device__ __forceinline__ void next(Cursor& c) const { c += gridDim.x; }
+  __device__ __forceinline__ Item item(const Cursor& c) const { return gitem(g, c); }
+  __device__ __forceinline__ int ktiles(int nm) const {
+    int nT = 0;
+    for (int k = 0; k < nm; ++k) nT += gitem(g, blockIdx.x + k * gridDim.x).len;
+    return nT;
+  }
+  template <bool ISA, bool KM>
+  __device__ __forceinline__ PPOperand operand() const { return {0, 0, 0, 0}; }
+  // the operand follows the stream's current problem
+  template <bool ISA, bool KM>
+  __device__ __forceinline__ PPStream stream(const Item& it, int k0, PPOperand& o) const {
+    const GroupProb& P = g.prob[it.pi];
     const int mode = ISA ? P.a_mode : P.b_mode;
     const int kseg = ISA ? P.a_kseg : P.b_kseg;
-    dk = (KM ? (int64_t)64 : (int64_t)64 * ld) * (int64_t)sizeof(T);
-    hk = dk / 2;
-    const int k0 = (iss_it.kt0 + iss_kt) * 64;
+    o = PPOperand::make<T, KM>(ISA ? P.lda : P.ldb, mode, kseg);
     int kl;
     const T* X = operand_base<T>(g.pool + (ISA ? P.a_off : P.b_off), mode, ISA ? P.sA0 : P.sB0,
-                                 0, iss_it.b0, 0, kseg, k0, kl);
-    const int r0 = ISA ? iss_it.m0 : iss_it.n0;
-    const char* sx = (const char*)(KM ? X + (int64_t)r0 * ld + kl : X + (int64_t)kl * ld + r0);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int e = 0; e < 2; ++e)
-        ps[h][e] = sx + (KM ? (int64_t)rowv[h][e] * ld + kkv[h][e]
-                            : (int64_t)kkv[h][e] * ld + rowv[h][e]) * (int64_t)sizeof(T);
-    left = (mode >= 2 ? kseg / 64 : 1 << 30) - (kl >> 6);
-  };
-  auto next_ktile = [&]() {
-    if (++iss_kt == iss_it.len) {
-      iss_kt = 0;
-      if (++iss_k < nm) {
-        iss_it = gitem(g, blockIdx.x + iss_k * G);
-        set_stream();
-      }
-    } else if (--left == 0) {
-      set_stream();
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int e = 0; e < 2; ++e) ps[h][e] += dk;
-    }
-  };
-  auto issue = [&](int kh_) {
-    const uint32_t dst = lbase + (kh_ & 3) * PP_SLOT + (ISA ? 0 : 16384) + 2 * wl * 1024;
-    const int64_t kh = (kh_ & 1) ? hk : 0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) glds16_at(ps[h][e] + kh, dst + (8 * h + e) * 1024);
-  };
-  bool ep_cur = false, ep_prev = false;
+                                 0, it.b0, 0, kseg, k0, kl);
+    const int r0 = ISA ? it.m0 : it.n0;
+    PPStream s;
+    s.base = (const char*)(KM ? X + (int64_t)r0 * o.ld + kl : X + (int64_t)kl * o.ld + r0);
+    s.left = o.seg - (kl >> 6);
+    s.rmax = 256;
+    return s;
+  }
   // dbg 32: the epilogue's stores are not counted, so every wait drains them too (the guard of
   // the counts: results must not change)
-  const int epo = (g.dbg & 32) ? 0 : EPO;
-  auto deadline = [&](int kh_) {                           // as pp2_run
-    if (kh_ >= nh) return;
-    const int m = kh_ - 1;
-    if constexpr (GRP == 0) {
-      const int n = (m + 2 < nh ? 4 : 0) + (ep_cur ? epo : 0);
-      if (n == 4) wait_vmcnt<4>();
-      else wait_vm_le(n);
-    } else {
-      const int n = (m + 2 < nh ? 4 : 0) + (m + 3 < nh ? 4 : 0) +
-                    ((ep_prev ? 1 : 0) + (ep_cur ? 1 : 0)) * epo;
-      if (n == 8) wait_vmcnt<8>();
-      else wait_vm_le(n);
-    }
-  };
-
-  set_stream();
-  if constexpr (GRP == 0) {
-    issue(0);
-    issue(1);
-    wait_vmcnt<4>();
-  } else {
-    issue(0);
-    if (nh > 1) issue(1);
-    if (nh > 2) {
-      next_ktile();
-      issue(2);
-    }
-    wait_vm_le((nh > 1 ? 4 : 0) + (nh > 2 ? 4 : 0));
+  __device__ __forceinline__ int epo() const {
+    return (g.dbg & 32) ? 0 : C::TM * C::TN + (SPL == 2 ? 2 : 0);
   }
-  __builtin_amdgcn_s_barrier();
-  if constexpr (GRP == 1) __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-
-  f32x4 acc[C::TM][C::TN];
-#pragma unroll
-  for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-    for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  F fa[8] = {}, fb[4] = {};
-  GItem cur = gitem(g, blockIdx.x);
-  int cur_k = 0, cur_left = cur.len;
-  float rsum[2] = {0.f, 0.f};
-  auto epilogue = [&]() {
+  __device__ __forceinline__ void epilogue(const Item& cur, f32x4 (&acc)[C::TM][C::TN],
+                                           float (&rsum)[2], const char*, int lane, int wm,
+                                           int wn) const {
     const GroupProb& P = g.prob[cur.pi];
     const int gq = lane >> 4, rl = lane & 15;
     const bool direct = P.splits == 1;
@@ -1324,11 +1091,137 @@ __device__ __forceinline__ void ppg_run(const GroupParams& g, uint32_t lbase, co
         rsum[h] = 0.f;
       }
     }
+  }
+};
+
+// One group's whole schedule over the items of `src` (nm of them for this block)
+template <typename T, bool AK, bool BK, int GRP, int SPL, class Src>
+__device__ __forceinline__ void pp2_run(const Src& src, uint32_t lbase, const char* smem, int nm) {
+  using C = CfgPP;
+  typedef typename Frag16<T>::t F;
+  constexpr bool ISA = GRP == 1;                           // this group's operand: A (else B)
+  constexpr bool KM = ISA ? AK : BK;
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wl = wid & 3;
+  constexpr int wm = GRP;
+  const int wn = wl;
+  const int nT = src.ktiles(nm);                           // K-tiles of this block's items
+  const int nh = 2 * nT;                                   // k-halves of the block's stream
+  // this wave's instructions 2 wl, 2 wl + 1 of each half (h) of its operand's k-half image: the
+  // row and k of each lane's 16-B chunk, relative to the operand's K-tile base
+  int rowv[2][2], kkv[2][2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+      chunk_src<T, KM, 64, 256>((8 * h + 2 * wl + e) * 64 + lane, rowv[h][e], kkv[h][e]);
+
+  // the issue stream: item iss_k, K-tile iss_kt of it, per-lane sources ps of that K-tile
+  typename Src::Cursor iss_c = src.first();
+  typename Src::Item iss_it = src.item(iss_c);
+  int iss_k = 0, iss_kt = 0, left = 0;
+  PPOperand op = src.template operand<ISA, KM>();
+  const char* ps[2][2];
+  auto set_stream = [&]() {
+    const PPStream s = src.template stream<ISA, KM>(iss_it, (iss_it.kt0 + iss_kt) * 64, op);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int r = Src::CLAMP ? min(rowv[h][e], s.rmax) : rowv[h][e];
+        ps[h][e] = s.base + (KM ? (int64_t)r * op.ld + kkv[h][e] : (int64_t)kkv[h][e] * op.ld + r) *
+                                (int64_t)sizeof(T);
+      }
+    left = s.left;
   };
+  auto next_ktile = [&]() {
+    if (++iss_kt == iss_it.len) {
+      iss_kt = 0;
+      if (++iss_k < nm) {
+        src.next(iss_c);
+        iss_it = src.item(iss_c);
+        set_stream();
+      }
+    } else if (--left == 0) {
+      set_stream();
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) ps[h][e] += op.dk;
+    }
+  };
+  // this wave's 4 instructions of k-half g (its operand's two halves) from the current K-tile
+  auto issue = [&](int g) {
+    const uint32_t dst = lbase + (g & 3) * PP_SLOT + (ISA ? 0 : 16384) + 2 * wl * 1024;
+    const int64_t kh = (g & 1) ? op.hk : 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) glds16_at(ps[h][e] + kh, dst + (8 * h + e) * 1024);
+  };
+  // epilogues issued in this phase's / the previous phase's load segment (deadline counts)
+  bool ep_cur = false, ep_prev = false;
+  const int epo = src.epo();
+  // k-half g retired by this wave (at phase g - 1); counts as in the header comment, rounded
+  // down near the stream's end
+  auto deadline = [&](int g) {
+    if (g >= nh) return;
+    const int m = g - 1;
+    if constexpr (GRP == 0) {
+      // younger: its piece of k-half m + 2 (phase m) and phase m's epilogue
+      const int n = (m + 2 < nh ? 4 : 0) + (ep_cur ? epo : 0);
+      if (n == 4) wait_vmcnt<4>();
+      else wait_vm_le(n);
+    } else {
+      // younger: its pieces of k-halves m + 2 (phase m - 1) and m + 3 (phase m)
+      const int n = (m + 2 < nh ? 4 : 0) + (m + 3 < nh ? 4 : 0) +
+                    ((ep_prev ? 1 : 0) + (ep_cur ? 1 : 0)) * epo;
+      if (n == 8) wait_vmcnt<8>();
+      else wait_vm_le(n);
+    }
+  };
+
+  // prologue: group 0 the B halves of k-halves 0, 1; group 1 the A halves of 0, 1, 2
+  set_stream();
+  if constexpr (GRP == 0) {
+    issue(0);
+    issue(1);
+    wait_vmcnt<4>();                                       // k-half 0 retired
+  } else {
+    issue(0);
+    if (nh > 1) issue(1);
+    if (nh > 2) {
+      next_ktile();
+      issue(2);
+    }
+    wait_vm_le((nh > 1 ? 4 : 0) + (nh > 2 ? 4 : 0));
+  }
+  __builtin_amdgcn_s_barrier();
+  if constexpr (GRP == 1) __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+
+  f32x4 acc[C::TM][C::TN];
+#pragma unroll
+  for (int i = 0; i < C::TM; ++i)
+#pragma unroll
+    for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  F fa[8] = {}, fb[4] = {};
+  typename Src::Cursor cur_c = src.first();
+  typename Src::Item cur = src.item(cur_c);
+  int cur_left = cur.len;
+  float rsum[2] = {0.f, 0.f};                              // SPL 2: row sums of sub-tiles wn, wn + 4
+  // a plain lambda around the forced-inline epilogue: the ordinary inliner places it once the
+  // kernel's LDS base is a constant, and persist_epilogue's test of bias_lds folds.  Called
+  // directly, hipcc kept that test and the scalar-load bias path behind it: about 40 more SGPR
+  // spills in every gemm_pp2_kernel (-Rpass-analysis=kernel-resource-usage)
+  auto epilogue = [&]() { src.epilogue(cur, acc, rsum, smem, lane, wm, wn); };
   for (int t = 0; t < nT; ++t) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const int m = 2 * t + ks;
+      // ---- load segment
       ep_prev = ep_cur;
       ep_cur = false;
       if (ks == 0) {
@@ -1339,11 +1232,13 @@ __device__ __forceinline__ void ppg_run(const GroupParams& g, uint32_t lbase, co
           for (int i = 0; i < C::TM; ++i)
 #pragma unroll
             for (int j = 0; j < C::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-          cur = gitem(g, blockIdx.x + (++cur_k) * G);
+          src.next(cur_c);
+          cur = src.item(cur_c);
           cur_left = cur.len;
         }
         --cur_left;
       }
+      // stream step: group 0 issues k-half m + 2 (K-tile t + 1), group 1 k-half m + 3
       if ((GRP == 0 && ks == 0) || (GRP == 1 && ks == 1)) next_ktile();
       const char* slot = smem + (m & 3) * PP_SLOT;
 #pragma unroll
@@ -1353,13 +1248,14 @@ __device__ __forceinline__ void ppg_run(const GroupParams& g, uint32_t lbase, co
       for (int i = 0; i < 8; ++i)
         fa[i] = read_frag16<T, AK, 64, 256>(slot, wm * C::WTM + 16 * i, 0);
       {
-        const int kh_ = m + (GRP == 0 ? 2 : 3);
-        if (kh_ < nh) issue(kh_);
+        const int g = m + (GRP == 0 ? 2 : 3);
+        if (g < nh) issue(g);
       }
       if constexpr (GRP == 1) deadline(m + 1);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
+      // ---- MFMA segment
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 8; ++i)
@@ -1378,10 +1274,54 @@ __device__ __forceinline__ void ppg_run(const GroupParams& g, uint32_t lbase, co
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  if constexpr (GRP == 0) __builtin_amdgcn_s_barrier();
+  if constexpr (GRP == 0) __builtin_amdgcn_s_barrier();    // balance group 1's extra barrier
   epilogue();
 }
 
+template <typename T, bool AK, bool BK, int EPI>
+__global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* bias_lds = (float*)(smem + PP_NSLOT * PP_SLOT);
+  const int W = p.tiles_m * p.tiles_n * p.batch0 * p.batch1;
+  const int G = gridDim.x;
+  const int nm = (W - (int)blockIdx.x + G - 1) / G;
+  if (p.bias_mode == 1) {
+    const int nb = (p.n_bias > 0 ? p.batch0 : 1) * p.N;
+    for (int i = threadIdx.x; i < nb; i += 512) {
+      const int b = i / p.N;
+      bias_lds[i] = (p.n_bias > 0 ? p.bias_tab[b] : p.bias)[i - b * p.N];
+    }
+  }
+  __syncthreads();
+  if (nm <= 0 || p.K < 64) return;
+  const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const GemmSrc<T, EPI, 0> src{p, W};
+  if ((threadIdx.x >> 6) < 4) pp2_run<T, AK, BK, 0, 0>(src, lbase, smem, nm);
+  else pp2_run<T, AK, BK, 1, 0>(src, lbase, smem, nm);
+}
+
+// split-K form (cfg 44, on the cfg 45 schedule): items are (tile, split) — the weight-gradient GEMMs (M, N = features,
+// K = B x T rows: a few 256 x 256 tiles over a long K); fp32 partial slabs (+ the A row sums) for
+// splitk_reduce_kernel, which jmt_gemm launches next
+// (An in-launch reduction — the S blocks of a tile meeting at a per-tile counter, then each
+// reducing its 256 / S rows over all S slabs — measured slower than the separate
+// splitk_reduce_kernel launch on every weight-gradient shape, 5-10 %: the reduce loop of one
+// 8-wave block per CU keeps too few slab loads in flight; profiles/r05/tn_fused_reduce_ab.txt.)
+
+template <typename T, bool AK, bool BK, int SPL>
+__global__ __launch_bounds__(512) void gemm_pp_split_kernel(GemmParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int W = p.tiles_m * p.tiles_n * p.batch0 * p.batch1 * p.splits;
+  const int G = gridDim.x;
+  const int nm = (W - (int)blockIdx.x + G - 1) / G;
+  if (nm <= 0 || p.K < 64) return;
+  const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const GemmSrc<T, 0, SPL> src{p, W};
+  if ((threadIdx.x >> 6) < 4) pp2_run<T, AK, BK, 0, SPL>(src, lbase, smem, nm);
+  else pp2_run<T, AK, BK, 1, SPL>(src, lbase, smem, nm);
+}
+
+// grouped split-K form (jmt_gemm_grouped): the same schedule over the items of GroupSrc
 template <typename T, bool AK, bool BK, int SPL>
 __global__ __launch_bounds__(512) void gemm_group_kernel(GroupParams g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1389,8 +1329,9 @@ __global__ __launch_bounds__(512) void gemm_group_kernel(GroupParams g) {
   const int nm = (g.W - (int)blockIdx.x + G - 1) / G;
   if (nm <= 0) return;
   const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  if ((threadIdx.x >> 6) < 4) ppg_run<T, AK, BK, 0, SPL>(g, lbase, smem, nm);
-  else ppg_run<T, AK, BK, 1, SPL>(g, lbase, smem, nm);
+  const GroupSrc<T, SPL> src{g};
+  if ((threadIdx.x >> 6) < 4) pp2_run<T, AK, BK, 0, SPL>(src, lbase, smem, nm);
+  else pp2_run<T, AK, BK, 1, SPL>(src, lbase, smem, nm);
 }
 
 // The group's reduce: block blockIdx.x serves the problem whose [rblk0, rblk0 + rblk_n) holds
@@ -1415,33 +1356,10 @@ __global__ __launch_bounds__(256) void group_reduce_kernel(GroupParams g) {
     const int m = (int)(mn / P.N), n = (int)(mn - (int64_t)m * P.N);
     const float* src0 = ws + (int64_t)b * per + mn;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    int s = 0;
-    for (; s + 8 <= S; s += 8) {
-      float4 t[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t[u] = *(const float4*)(src0 + (s + u) * sstride);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        v[0] += t[u].x; v[1] += t[u].y; v[2] += t[u].z; v[3] += t[u].w;
-      }
-    }
-    for (; s < S; ++s) {
-      const float4 t = *(const float4*)(src0 + s * sstride);
-      v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
-    }
+    sum_splits4(src0, sstride, S, v);
     if (P.d_off >= 0 && n == 0 && g.pool[P.d_off + b]) {   // the A row sums' split partials
       const float* src = g.ws + P.rs_off + (int64_t)b * P.M + m;
-      const int64_t ts = (int64_t)nb * P.M;
-      float r = 0.f;
-      int t = 0;
-      for (; t + 8 <= S; t += 8) {
-        float x[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = src[(t + u) * ts];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) r += x[u];
-      }
-      for (; t < S; ++t) r += src[t * ts];
+      const float r = sum_splits_row(src, (int64_t)nb * P.M, S);
       float* d = (float*)const_cast<void*>(g.pool[P.d_off + b]);
       d[m] = (P.dbias_acc ? d[m] : 0.f) + r;
     }
@@ -1555,19 +1473,26 @@ static void launch_persist_cfg(const GemmParams& p, int blocks, hipStream_t st, 
   }
 }
 
-template <typename T, class C>
-static void launch_persist_t(const GemmParams& p, int ak, int bk, int blocks, hipStream_t st,
-                             int cfg) {
-  if (ak && bk) launch_persist_cfg<T, true, true, C>(p, blocks, st, cfg);
-  else if (ak) launch_persist_cfg<T, true, false, C>(p, blocks, st, cfg);
-  else if (bk) launch_persist_cfg<T, false, true, C>(p, blocks, st, cfg);
-  else launch_persist_cfg<T, false, false, C>(p, blocks, st, cfg);
+// f(Tag<T>, bool_constant<AK>, bool_constant<BK>) for the 16-bit dtype and the operands' layouts
+template <typename T> struct Tag { using type = T; };
+template <class F>
+static void for_layout(int dt, int ak, int bk, F f) {
+  auto layouts = [&](auto t) {
+    if (ak && bk) f(t, std::true_type{}, std::true_type{});
+    else if (ak) f(t, std::true_type{}, std::false_type{});
+    else if (bk) f(t, std::false_type{}, std::true_type{});
+    else f(t, std::false_type{}, std::false_type{});
+  };
+  if (dt == JMT_BF16) layouts(Tag<__bf16>{});
+  else layouts(Tag<_Float16>{});
 }
 
 int launch_gemm_persist(const GemmParams& p, int dt, int ak, int bk, int cfg, int blocks,
                         hipStream_t st) {
-  if (dt == JMT_BF16) launch_persist_t<__bf16, Cfg40>(p, ak, bk, blocks, st, cfg);
-  else launch_persist_t<_Float16, Cfg40>(p, ak, bk, blocks, st, cfg);
+  for_layout(dt, ak, bk, [&](auto t, auto a, auto b) {
+    launch_persist_cfg<typename decltype(t)::type, decltype(a)::value, decltype(b)::value, Cfg40>(
+        p, blocks, st, cfg);
+  });
   return 0;
 }
 
@@ -1580,21 +1505,14 @@ static void launch_pp_split_t(const GemmParams& p, bool rs, int blocks, hipStrea
   hipLaunchKernelGGL(fn, dim3(blocks), dim3(512), (size_t)PP_NSLOT * PP_SLOT, st, p);
 }
 
-template <typename T>
-static void launch_pp_split_l(const GemmParams& p, int ak, int bk, bool rs, int blocks,
-                              hipStream_t st) {
-  if (ak && bk) launch_pp_split_t<T, true, true>(p, rs, blocks, st);
-  else if (ak) launch_pp_split_t<T, true, false>(p, rs, blocks, st);
-  else if (bk) launch_pp_split_t<T, false, true>(p, rs, blocks, st);
-  else launch_pp_split_t<T, false, false>(p, rs, blocks, st);
-}
-
 // the split-K ping-pong launch (cfg 44): p.splits, p.tiles_m / tiles_n (256 x 256), p.ws and
 // (row sums) p.dbias_ws set by the caller; the caller launches the slab reduction after it
 void launch_gemm_pp_split(const GemmParams& p, int dt, int ak, int bk, bool rs, int blocks,
                           hipStream_t st) {
-  if (dt == JMT_BF16) launch_pp_split_l<__bf16>(p, ak, bk, rs, blocks, st);
-  else launch_pp_split_l<_Float16>(p, ak, bk, rs, blocks, st);
+  for_layout(dt, ak, bk, [&](auto t, auto a, auto b) {
+    launch_pp_split_t<typename decltype(t)::type, decltype(a)::value, decltype(b)::value>(
+        p, rs, blocks, st);
+  });
 }
 
 template <typename T, bool AK, bool BK>
@@ -1605,19 +1523,12 @@ static void launch_group_t(const GroupParams& g, bool rs, int blocks, hipStream_
   hipLaunchKernelGGL(fn, dim3(blocks), dim3(512), (size_t)PP_NSLOT * PP_SLOT, st, g);
 }
 
-template <typename T>
-static void launch_group_l(const GroupParams& g, int ak, int bk, bool rs, int blocks,
-                           hipStream_t st) {
-  if (ak && bk) launch_group_t<T, true, true>(g, rs, blocks, st);
-  else if (ak) launch_group_t<T, true, false>(g, rs, blocks, st);
-  else if (bk) launch_group_t<T, false, true>(g, rs, blocks, st);
-  else launch_group_t<T, false, false>(g, rs, blocks, st);
-}
-
 void launch_gemm_group(const GroupParams& g, int dt, int ak, int bk, bool rs, int blocks,
                        hipStream_t st) {
-  if (dt == JMT_BF16) launch_group_l<__bf16>(g, ak, bk, rs, blocks, st);
-  else launch_group_l<_Float16>(g, ak, bk, rs, blocks, st);
+  for_layout(dt, ak, bk, [&](auto t, auto a, auto b) {
+    launch_group_t<typename decltype(t)::type, decltype(a)::value, decltype(b)::value>(
+        g, rs, blocks, st);
+  });
 }
 
 void launch_group_reduce(const GroupParams& g, int blocks, hipStream_t st) {

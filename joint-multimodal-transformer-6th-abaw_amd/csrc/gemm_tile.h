@@ -579,6 +579,59 @@ __device__ __forceinline__ void load4_guard(const O* row, int n, int lim, bool v
   }
 }
 
+// v += the S splits' partials of 4 consecutive outputs (src0, sstride floats from split to
+// split), in split order — the order is what makes every reduce of the same slabs bit-identical.
+// (every slab load of up to 32 splits issued before the first add measured slower: 19.7 vs
+// 17.3 us per reduce launch in the c3 step, profiles/r06/reduce_prof_all_loads_first.csv vs reduce_prof_rowsum_batched.csv)
+// (two lanes per output group, each summing half of the splits, then lo + hi: slower in
+// the c3 step, 4.014-4.024 vs 4.001-4.011 ms, profiles/r06/step_ab_skr_pair.txt)
+// eight (then four) slab loads in flight per step (the same sums as four at a time:
+// bit-identical; no measurable change in the step, profiles/r04/splitk_reduce_depth_ab.txt)
+__device__ __forceinline__ void sum_splits4(const float* src0, int64_t sstride, int S,
+                                            float (&v)[4]) {
+  int s = 0;
+  for (; s + 8 <= S; s += 8) {
+    float4 t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[u] = *(const float4*)(src0 + (s + u) * sstride);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      v[0] += t[u].x; v[1] += t[u].y; v[2] += t[u].z; v[3] += t[u].w;
+    }
+  }
+  for (; s + 4 <= S; s += 4) {
+    float4 t[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t[u] = *(const float4*)(src0 + (s + u) * sstride);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      v[0] += t[u].x; v[1] += t[u].y; v[2] += t[u].z; v[3] += t[u].w;
+    }
+  }
+  for (; s < S; ++s) {
+    const float4 t = *(const float4*)(src0 + s * sstride);
+    v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
+  }
+}
+
+// the S splits' partials of one A row sum (src, ts floats from split to split), in split order:
+// eight loads in flight per step (a plain loop issued them one at a time behind each add: ~20
+// dependent HBM round trips for the column-0 threads at 21 splits, the tail of every row-summing
+// reduce launch)
+__device__ __forceinline__ float sum_splits_row(const float* src, int64_t ts, int S) {
+  float r = 0.f;
+  int t = 0;
+  for (; t + 8 <= S; t += 8) {
+    float x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) x[u] = src[(t + u) * ts];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) r += x[u];
+  }
+  for (; t < S; ++t) r += src[t * ts];
+  return r;
+}
+
 // The reduce + epilogue of W (1 or 4) consecutive outputs (b, m, n..n+W-1): the splits' fp32
 // partial slabs summed in split order (the same order, so the same bits, wherever it runs),
 // then alpha, bias, beta * C, ReLU, the ReLU mask; the A row sums' split partials folded by the
@@ -593,60 +646,15 @@ __device__ __forceinline__ void reduce_outputs(const GemmParams& p, int b, int m
   for (int i = 0; i < W; ++i) v[i] = 0.f;
   const int64_t sstride = (int64_t)nb * per;
   const float* src0 = p.ws + (int64_t)b * per + mn;
-  int s = 0;
   if constexpr (W == 4) {
-    // (every slab load of up to 32 splits issued before the first add measured slower: 19.7 vs
-    // 17.3 us per reduce launch in the c3 step, profiles/r06/reduce_prof_all_loads_first.csv vs reduce_prof_rowsum_batched.csv)
-    // (two lanes per output group, each summing half of the splits, then lo + hi: slower in
-    // the c3 step, 4.014-4.024 vs 4.001-4.011 ms, profiles/r06/step_ab_skr_pair.txt)
-    // eight (then four) slab loads in flight per step, summed in split order (the same sums as
-    // four at a time: bit-identical; no measurable change in the step, profiles/r04/
-    // splitk_reduce_depth_ab.txt)
-    for (; s + 8 <= p.splits; s += 8) {
-      float4 t[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t[u] = *(const float4*)(src0 + (s + u) * sstride);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        v[0] += t[u].x; v[1] += t[u].y; v[2] += t[u].z; v[3] += t[u].w;
-      }
-    }
-    for (; s + 4 <= p.splits; s += 4) {
-      float4 t[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) t[u] = *(const float4*)(src0 + (s + u) * sstride);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        v[0] += t[u].x; v[1] += t[u].y; v[2] += t[u].z; v[3] += t[u].w;
-      }
-    }
-  }
-  for (; s < p.splits; ++s) {
-    const float* src = src0 + s * sstride;
-    if constexpr (W == 4) {
-      const float4 t = *(const float4*)src;
-      v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
-    } else {
-      v[0] += *src;
-    }
+    sum_splits4(src0, sstride, p.splits, v);
+  } else {
+    for (int s = 0; s < p.splits; ++s) v[0] += src0[s * sstride];
   }
   const int b0 = b / p.batch1, b1 = b % p.batch1;
   if (p.n_dbias > 0 && n == 0 && p.dbias_tab[b0]) {   // the A row sums' split partials
     const float* src = p.dbias_ws + (int64_t)b * p.M + m;
-    const int64_t ts = (int64_t)nb * p.M;
-    float r = 0.f;
-    int t = 0;
-    // eight loads in flight per step, summed in split order (a plain loop issued them one at a
-    // time behind each add: ~20 dependent HBM round trips for the column-0 threads at 21 splits,
-    // the tail of every row-summing reduce launch)
-    for (; t + 8 <= p.splits; t += 8) {
-      float x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) x[u] = src[(t + u) * ts];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) r += x[u];
-    }
-    for (; t < p.splits; ++t) r += src[t * ts];
+    const float r = sum_splits_row(src, (int64_t)nb * p.M, p.splits);
     float* d = p.dbias_tab[b0];
     d[m] = (p.dbias_acc ? d[m] : 0.f) + r;
   }

@@ -5,7 +5,8 @@ the weight-gradient queue of jmt.ops that feeds it from the training step.
 
 The shapes are the smallest at which each mechanism can go wrong: a single tile, a pointer-table
 batch, per-batch K-segments whose split ranges start inside a segment, a problem short enough to
-take one split and write C directly, and more items than CUs (the second round of the walk)."""
+take one split and write C directly, and more items than CUs (the second round of the walk),
+with problems of one shape and with a second item of another shape than the first."""
 import ctypes as C
 import os
 import subprocess
@@ -310,6 +311,51 @@ def test_more_items_than_cus():
     assert sp == [8] * 9
     for i, p in enumerate(probs):
         p.check(f"nine p{i}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ak,bk", [(False, False), (True, True), (True, False), (False, True)])
+def test_second_item_of_another_shape_bit_identical(ak, bk):
+    """The schedule's stream crossing from one problem shape to another inside a block, for every
+    layout.  Two shapes alternate: 256 x 512 over K = 1024 as two 512-row segments per batch entry
+    (a_mode = b_mode = 3), forced to 4 splits of 4 K-tiles, so splits 1 and 3 begin inside a
+    segment; and 512 x 256 over K = 512, forced to 2 splits.  No knob shrinks the grid, so the
+    launch must hold more items than CUs, as in test_more_items_than_cus.  One entry of each shape
+    is 8 + 4 items, and a call takes 16 problems at most (128 items), so each problem has three
+    batch entries instead: 8 x (24 + 12) = 288 items.  A grid of 256 gives each XCD 36 consecutive
+    logical items — one pair of problems — and a block's second item lies 32 items behind its
+    first: in the pair's 512 x 256 problem when the first is one of the first four of the
+    256 x 512 one.  Each problem's C (and, TN, the row sums) must have the bits of
+    ops.gemm(splits=...) on it alone under cfg 44, the comparison of
+    test_mixed_group_vs_fp32_and_bit_identity."""
+    lib = _lib.load()
+    gen = torch.Generator(device=DEV).manual_seed(11)
+    rs = not ak and not bk
+    probs = []
+    for i in range(8):
+        probs.append(_Prob(256, 512, 512, 2, 3, ak, bk, gen, table=True, dbias=rs and i < 4,
+                           splits=4))
+        probs.append(_Prob(512, 256, 512, 1, 3, ak, bk, gen, table=True, dbias=False, splits=2))
+    sp = _run_group(probs)
+    assert sp == [4, 2] * 8
+    items = sum((p.M // 256) * (p.N // 256) * p.nb * s for p, s in zip(probs, sp))
+    assert items == 288
+    for i, p in enumerate(probs):
+        p.check(f"two shapes[{ak},{bk}] p{i}")
+    got = [(p.C.clone(), [d.clone() if d is not None else None for d in p.db] if p.db else None)
+           for p in probs]
+    for i, p in enumerate(probs):
+        p.fresh()
+        lib.jmt_gemm_set_debug(44 << 8)
+        try:
+            ops.gemm(splits=sp[i], **p.kwargs())
+            torch.cuda.synchronize()
+        finally:
+            lib.jmt_gemm_set_debug(0)
+        assert torch.equal(p.C, got[i][0]), (i, "C differs from jmt_gemm alone")
+        if p.db:
+            for a, b in zip(p.db, got[i][1]):
+                assert a is None or torch.equal(a, b), (i, "row sums differ from jmt_gemm alone")
 
 
 _STEP_SCRIPT = r"""

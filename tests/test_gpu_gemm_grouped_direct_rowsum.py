@@ -1,5 +1,5 @@
 """jmt_gemm_grouped: a problem with ONE split and a dbias table finishes its A row sums in the GEMM
-kernel (csrc/gemm_persist.hip ppg_run: the item of column panel 0 writes dbias_tab[b0][m], the
+kernel (csrc/gemm_persist.hip GroupSrc::epilogue: the item of column panel 0 writes dbias_tab[b0][m], the
 other items store into an area nobody reads), so row sums no longer force a second split
 (csrc/gemm.hip group_plan) and such a problem takes neither a slab nor a block of the reduce.
 
