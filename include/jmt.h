@@ -404,6 +404,41 @@ int jmt_head_bwd(int h_dt, int gy_dt, int64_t rows, int hid, int k, const void* 
                  float* db2_1, float* partials, void* stream);
 size_t jmt_head_bwd_workspace_bytes(int64_t rows);
 
+/* ------------------------------------------------------------------ regressor dropout
+ * Dropout between the regressors' ReLU and output layer (two_transformers.py:104-114, v_dropout /
+ * a_dropout) with a counter-based mask that the backward regenerates and nothing stores.
+ * Generator: Philox4x32-10.  Device state block: uint32[4] = seed_lo, seed_hi, call, stream.
+ * Key (seed_lo, seed_hi); counter (row, quad, call, stream) with row the memory row of the
+ * masked buffer (rows < 2^32) and quad = column / 4; output word i belongs to column 4 quad + i.
+ * An element is kept iff word >= (uint32)((double)p * 2^32) (p = 0 keeps everything) and then
+ * multiplied by s = 1.0f / (1.0f - p) in fp32, otherwise it becomes 0.  Columns < split use p0,
+ * the others p1 (the V and A halves of [h_v | h_a]).  0 <= p < 1.
+ * jmt_dropout_next: out[0..3] = state[0..3], then state[2] += 1 (one thread): `out` is what one
+ *   forward keeps for its backward; a replayed graph draws a new call per replay.
+ * jmt_dropout: y = m . x over (rows x cols) of dtype dt (f32 / bf16 / f16) at row strides ldx /
+ *   ldy, in place (y == x) or not; cols and split multiples of 4, rows of x and y 8-B aligned;
+ *   ctr: a device uint32[4] written by jmt_dropout_next.
+ * jmt_head_fwd_drop / jmt_head_bwd_drop: jmt_head_fwd / jmt_head_bwd on h~ = m . h with the mask
+ *   of the (rows x 256) buffer h (split = 128), formed in registers: the forward dots and the
+ *   dw2 sums use h~, dh[r][j] = [h~ > 0] s sum_o gy[r][o] W2[o][j].
+ * jmt_dropout_reference: host only, no GPU call: out[r * cols + c] = the multiplier (0 or s) of
+ *   element (r, c) under the host array ctr, from the header the kernels compile. */
+int jmt_dropout_next(uint32_t* state, uint32_t* out, void* stream);
+int jmt_dropout(int dt, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows,
+                int64_t cols, int64_t split, float p0, float p1, const uint32_t* ctr,
+                void* stream);
+int jmt_head_fwd_drop(int h_dt, int y_dt, int64_t rows, int hid, int k, const void* h,
+                      int64_t ldh, const void* w2_0, const void* w2_1, const float* b2_0,
+                      const float* b2_1, void* y_0, void* y_1, int64_t ldy, float p0, float p1,
+                      const uint32_t* ctr, void* stream);
+int jmt_head_bwd_drop(int h_dt, int gy_dt, int64_t rows, int hid, int k, const void* h,
+                      int64_t ldh, const void* w2_0, const void* w2_1, const void* gy_0,
+                      const void* gy_1, int64_t ldgy, void* dh, int64_t lddh, float* dw2_0,
+                      float* dw2_1, float* db2_0, float* db2_1, float* partials, float p0,
+                      float p1, const uint32_t* ctr, void* stream);
+int jmt_dropout_reference(const uint32_t ctr[4], int64_t rows, int64_t cols, int64_t split,
+                          float p0, float p1, float* out);
+
 /* ------------------------------------------------------------------ CCC losses
  * kind 0: losses/loss.py:8-32 CCCLoss (digitize_num k; k>1: pred is (n,k) logits, softmax over
  *         bins = linspace(range) first)

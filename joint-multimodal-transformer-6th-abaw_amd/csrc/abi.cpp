@@ -4,6 +4,7 @@
 #include <stdio.h>
 
 #include "../../include/jmt.h"
+#include "dropout.h"
 
 namespace jmt {
 
@@ -40,5 +41,29 @@ extern "C" long long jmt_bounds_violations(int reset) {
   return n;
 }
 extern "C" const char* jmt_last_error(void) { return jmt::g_err; }
+
+// Host reference of the dropout mask: the multiplier (0 or s) of every element of a
+// (rows x cols) block, from the header the kernels compile (dropout.h).
+extern "C" int jmt_dropout_reference(const uint32_t ctr[4], int64_t rows, int64_t cols,
+                                     int64_t split, float p0, float p1, float* out) {
+  using namespace jmt;
+  if (!ctr || !out) return set_error(JMT_ERR_ARG, "jmt_dropout_reference: null pointer");
+  if (rows < 0 || rows >= ((int64_t)1 << 32))
+    return set_error(JMT_ERR_ARG, "jmt_dropout_reference: rows = %lld (the counter holds 32 "
+                     "bits of row)", (long long)rows);
+  if (cols < 0 || cols % 4 || split < 0 || split > cols || split % 4)
+    return set_error(JMT_ERR_ARG, "jmt_dropout_reference: cols = %lld / split = %lld must be "
+                     "multiples of 4, split in [0, cols]", (long long)cols, (long long)split);
+  if (!(p0 >= 0.f && p0 < 1.f && p1 >= 0.f && p1 < 1.f))
+    return set_error(JMT_ERR_ARG, "jmt_dropout_reference: rates must be in [0, 1)");
+  const uint32_t T[2] = {dropout_threshold(p0), dropout_threshold(p1)};
+  const float s[2] = {dropout_scale(p0), dropout_scale(p1)};
+  for (int64_t r = 0; r < rows; ++r)
+    for (int64_t q = 0; q < cols / 4; ++q) {
+      const int g = 4 * q < split ? 0 : 1;
+      dropout_quad(ctr, (uint32_t)r, (uint32_t)q, T[g], s[g], out + r * cols + 4 * q);
+    }
+  return JMT_OK;
+}
 // GEMM (3 dtypes x 4 layouts + split-K reduce) + row ops + CCC + SGD; informational only.
 extern "C" int jmt_kernel_count(void) { return 12 + 1 + 8 + 4 + 2 + 4; }

@@ -506,6 +506,102 @@ int main() {
   expect_err("gather null", jmt_gather_rows(JMT_F32, JMT_BF16, 4, 512, nullptr, 512, 4, nullptr,
                                             nullptr, 512, nullptr));
 
+  // regressor dropout: state tick, mask kernel, the head kernels' DROP entries, host reference
+  {
+    uint32_t* ual = (uint32_t*)algn;
+    const int64_t big = (int64_t)1 << 32;
+    expect_rc("dropout_next null state", jmt_dropout_next(nullptr, ual, nullptr), JMT_ERR_ARG,
+              "null state");
+    expect_rc("dropout_next null out", jmt_dropout_next(ual, nullptr, nullptr), JMT_ERR_ARG,
+              "null out");
+    expect_rc("dropout null ctr", jmt_dropout(JMT_BF16, algn, 256, algn, 256, 8, 256, 128, 0.3f,
+                                              0.5f, nullptr, nullptr), JMT_ERR_ARG,
+              "null counter");
+    expect_rc("dropout p = 1", jmt_dropout(JMT_BF16, algn, 256, algn, 256, 8, 256, 128, 0.3f,
+                                           1.0f, ual, nullptr), JMT_ERR_ARG, "[0, 1)");
+    expect_rc("dropout negative p", jmt_dropout(JMT_BF16, algn, 256, algn, 256, 8, 256, 128,
+                                                -0.1f, 0.5f, ual, nullptr), JMT_ERR_ARG,
+              "[0, 1)");
+    expect_rc("dropout cols 6", jmt_dropout(JMT_BF16, algn, 8, algn, 8, 8, 6, 4, 0.3f, 0.5f, ual,
+                                            nullptr), JMT_ERR_ARG, "multiple of 4");
+    expect_rc("dropout split 6", jmt_dropout(JMT_BF16, algn, 8, algn, 8, 8, 8, 6, 0.3f, 0.5f,
+                                             ual, nullptr), JMT_ERR_ARG, "split");
+    expect_rc("dropout misaligned", jmt_dropout(JMT_BF16, (void*)(buf + 2), 256, algn, 256, 8,
+                                                256, 128, 0.3f, 0.5f, ual, nullptr), JMT_ERR_ARG,
+              "8-B aligned");
+    expect_rc("dropout odd f32 stride", jmt_dropout(JMT_F32, algn, 257, algn, 256, 8, 256, 128,
+                                                    0.3f, 0.5f, ual, nullptr), JMT_ERR_ARG,
+              "8-B aligned");
+    expect_rc("dropout rows 2^32", jmt_dropout(JMT_BF16, algn, 256, algn, 256, big, 256, 128,
+                                               0.3f, 0.5f, ual, nullptr), JMT_ERR_ARG,
+              "32 bits of row");
+    expect_rc("dropout dtype", jmt_dropout(7, algn, 256, algn, 256, 8, 256, 128, 0.3f, 0.5f, ual,
+                                           nullptr), JMT_ERR_ARG, "dtype");
+    expect_rc("head_fwd_drop null ctr",
+              jmt_head_fwd_drop(JMT_BF16, JMT_F32, 8, 128, 1, algn, 256, algn, algn, nullptr,
+                                nullptr, algn, algn, 1, 0.3f, 0.5f, nullptr, nullptr),
+              JMT_ERR_ARG, "null counter");
+    expect_rc("head_fwd_drop p = 1",
+              jmt_head_fwd_drop(JMT_BF16, JMT_F32, 8, 128, 1, algn, 256, algn, algn, nullptr,
+                                nullptr, algn, algn, 1, 1.0f, 0.5f, ual, nullptr),
+              JMT_ERR_ARG, "[0, 1)");
+    expect_rc("head_fwd_drop rows 2^32",
+              jmt_head_fwd_drop(JMT_BF16, JMT_F32, big, 128, 1, algn, 256, algn, algn, nullptr,
+                                nullptr, algn, algn, 1, 0.3f, 0.5f, ual, nullptr),
+              JMT_ERR_ARG, "32 bits of row");
+    expect_rc("head_fwd_drop misaligned",
+              jmt_head_fwd_drop(JMT_BF16, JMT_F32, 8, 128, 1, misal, 256, algn, algn, nullptr,
+                                nullptr, algn, algn, 1, 0.3f, 0.5f, ual, nullptr),
+              JMT_ERR_ARG, "8-B aligned");
+    expect_rc("head_bwd_drop null ctr",
+              jmt_head_bwd_drop(JMT_BF16, JMT_F32, 8, 128, 1, algn, 256, algn, algn, algn, algn,
+                                1, algn, 256, nullptr, nullptr, nullptr, nullptr, (float*)algn,
+                                0.3f, 0.5f, nullptr, nullptr),
+              JMT_ERR_ARG, "null counter");
+    expect_rc("head_bwd_drop p = 1",
+              jmt_head_bwd_drop(JMT_BF16, JMT_F32, 8, 128, 1, algn, 256, algn, algn, algn, algn,
+                                1, algn, 256, nullptr, nullptr, nullptr, nullptr, (float*)algn,
+                                0.3f, 1.0f, ual, nullptr),
+              JMT_ERR_ARG, "[0, 1)");
+    expect_rc("head_bwd_drop rows 2^32",
+              jmt_head_bwd_drop(JMT_BF16, JMT_F32, big, 128, 1, algn, 256, algn, algn, algn,
+                                algn, 1, algn, 256, nullptr, nullptr, nullptr, nullptr,
+                                (float*)algn, 0.3f, 0.5f, ual, nullptr),
+              JMT_ERR_ARG, "32 bits of row");
+    expect_rc("head_bwd_drop misaligned dh",
+              jmt_head_bwd_drop(JMT_BF16, JMT_F32, 8, 128, 1, algn, 256, algn, algn, algn, algn,
+                                1, misal, 256, nullptr, nullptr, nullptr, nullptr, (float*)algn,
+                                0.3f, 0.5f, ual, nullptr),
+              JMT_ERR_ARG, "bad gradient buffers");
+    const uint32_t hctr[4] = {1u, 2u, 3u, 4u};
+    float m8[8];
+    expect_rc("dropout_reference null", jmt_dropout_reference(nullptr, 1, 4, 4, 0.f, 0.f, m8),
+              JMT_ERR_ARG, "null pointer");
+    expect_rc("dropout_reference p = 1", jmt_dropout_reference(hctr, 1, 4, 4, 1.0f, 0.f, m8),
+              JMT_ERR_ARG, "[0, 1)");
+    expect_rc("dropout_reference cols 6", jmt_dropout_reference(hctr, 1, 6, 4, 0.1f, 0.f, m8),
+              JMT_ERR_ARG, "multiples of 4");
+    expect_rc("dropout_reference rows 2^32", jmt_dropout_reference(hctr, big, 4, 4, 0.1f, 0.f,
+                                                                   m8), JMT_ERR_ARG,
+              "32 bits of row");
+    // valid call: every element is 0 or s, p = 0 keeps everything (ASan sees the writes)
+    expect_eq("dropout_reference ok", jmt_dropout_reference(hctr, 2, 4, 4, 0.f, 0.5f, m8), JMT_OK);
+    for (int i = 0; i < 8; ++i)
+      if (m8[i] != 1.f) {
+        fprintf(stderr, "FAIL dropout_reference p = 0: m[%d] = %g\n", i, m8[i]);
+        ++g_fail;
+      }
+    expect_eq("dropout_reference ok", jmt_dropout_reference(hctr, 1, 8, 4, 0.5f, 0.75f, m8),
+              JMT_OK);
+    for (int i = 0; i < 8; ++i) {
+      const float s = i < 4 ? 2.f : 4.f;
+      if (m8[i] != 0.f && m8[i] != s) {
+        fprintf(stderr, "FAIL dropout_reference: m[%d] = %g\n", i, m8[i]);
+        ++g_fail;
+      }
+    }
+  }
+
   if (jmt_bounds_violations(0) != -1) {
     fprintf(stderr, "FAIL bounds counters present in the default build\n");
     ++g_fail;

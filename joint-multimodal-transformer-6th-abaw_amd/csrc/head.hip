@@ -8,6 +8,8 @@
 //   backward: dh_g[r][j] = [h_g[r][j] > 0] sum_o gy_g[r][o] W2_g[o][j]     (16-bit out)
 //             dW2_g[o][j] += sum_r gy_g[r][o] h_g[r][j],  db2_g[o] += sum_r gy_g[r][o]
 // k = nout <= 24 (1 for the V / A regressors, 20 for configs[4]'s expression-style head).
+// With dropout (v_dropout / a_dropout > 0, the jmt_head_*_drop entries) h above is h~ = m . h,
+// the mask m regenerated per lane from its counter (dropout.h), and dh carries the scale s.
 //
 // A wave owns one row at a time: lanes 0-31 head 0, lanes 32-63 head 1, each lane 4 consecutive
 // hidden units, so a row of h is one 512-B coalesced access; the k dot products reduce over the
@@ -22,6 +24,7 @@
 // (16 us), the M = 1 fp32 weight-gradient GEMM with its 256-way split-K (36 us) and the bias
 // column sum; HBM-bound: the kernels read h once (9.8 MB) and write dh once.
 #include "common.h"
+#include "dropout.h"
 
 namespace jmt {
 
@@ -87,8 +90,25 @@ struct HeadArgs {
   int k;
 };
 
-template <typename TH, typename TY, int K>
-__global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
+// Dropout between the ReLU and the output layers (the DROP instantiations: jmt_head_*_drop).  A
+// lane's 4 hidden units are quad `lane` of row r of the (rows x 256) buffer: one Philox call
+// (dropout.h) gives their multipliers, h~ = m . h is formed in fp32 registers and never stored.
+struct HeadDrop {
+  uint32_t T[2];         // keep thresholds of the two halves
+  float s[2];            // 1 / (1 - p) of the two halves
+  const uint32_t* ctr;   // the forward's copy of the state block (jmt_dropout_next)
+};
+
+// The DROP kernels take HeadArgs with the mask arguments appended; the plain ones keep their
+// parameter (and with it their code, down to the offsets of the implicit arguments).
+struct HeadArgsDrop : HeadArgs {
+  HeadDrop dr;
+};
+template <bool DROP> struct HeadParam { typedef HeadArgs t; };
+template <> struct HeadParam<true> { typedef HeadArgsDrop t; };
+
+template <typename TH, typename TY, int K, bool DROP>
+__global__ __launch_bounds__(256) void head_fwd_kernel(typename HeadParam<DROP>::t a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = lane >> 5, c = 4 * (lane & 31);
   const int k = K == 1 ? 1 : a.k;
@@ -99,12 +119,26 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
     if (o < k) V4l<TH>::ld(W + o * HD_HID + c, wv[o]);
   const float* bp = a.b2[g];
   TY* yp = (TY*)a.y[g];
+  uint32_t ctr[4] = {0u, 0u, 0u, 0u}, dT = 0u;
+  float ds = 1.f;
+  if constexpr (DROP) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ctr[e] = a.dr.ctr[e];
+    dT = g ? a.dr.T[1] : a.dr.T[0];
+    ds = g ? a.dr.s[1] : a.dr.s[0];
+  }
   const int64_t r0 = ((int64_t)blockIdx.x * 4 + w) * HD_RPW;
   for (int i = 0; i < HD_RPW; ++i) {
     const int64_t r = r0 + i;
     if (r >= a.rows) break;
     float hv[4];
     V4l<TH>::ld((const TH*)a.h + r * a.ldh + g * HD_HID + c, hv);
+    if (DROP) {
+      float m[4];
+      dropout_quad(ctr, (uint32_t)r, (uint32_t)lane, dT, ds, m);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) hv[e] *= m[e];
+    }
 #pragma unroll
     for (int o = 0; o < K; ++o) {
       if (o < k) {            // (no break: the loop must unroll to keep wv in registers)
@@ -116,8 +150,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
   }
 }
 
-template <typename TH, typename TG, int K>
-__global__ __launch_bounds__(256) void head_bwd_kernel(HeadArgs a) {
+template <typename TH, typename TG, int K, bool DROP>
+__global__ __launch_bounds__(256) void head_bwd_kernel(typename HeadParam<DROP>::t a) {
   __shared__ float red[2][HD_KMAX * HD_HID + HD_KMAX];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = lane >> 5, c = 4 * (lane & 31);
@@ -132,12 +166,26 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadArgs a) {
     for (int e = 0; e < 4; ++e) aw[o][e] = 0.f;
   }
   const TG* gp = (const TG*)a.gy[g];
+  uint32_t ctr[4] = {0u, 0u, 0u, 0u}, dT = 0u;
+  float ds = 1.f;
+  if constexpr (DROP) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ctr[e] = a.dr.ctr[e];
+    dT = g ? a.dr.T[1] : a.dr.T[0];
+    ds = g ? a.dr.s[1] : a.dr.s[0];
+  }
   const int64_t r0 = ((int64_t)blockIdx.x * 4 + w) * HD_RPW;
   for (int i = 0; i < HD_RPW; ++i) {
     const int64_t r = r0 + i;
     if (r >= a.rows) break;
     float hv[4], d[4] = {0.f, 0.f, 0.f, 0.f};
     V4l<TH>::ld((const TH*)a.h + r * a.ldh + g * HD_HID + c, hv);
+    if (DROP) {
+      float m[4];
+      dropout_quad(ctr, (uint32_t)r, (uint32_t)lane, dT, ds, m);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) hv[e] *= m[e];
+    }
 #pragma unroll
     for (int o = 0; o < K; ++o) {
       if (o < k) {
@@ -151,7 +199,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadArgs a) {
       }
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) d[e] = hv[e] > 0.f ? d[e] : 0.f;
+    for (int e = 0; e < 4; ++e) d[e] = hv[e] > 0.f ? (DROP ? ds * d[e] : d[e]) : 0.f;
     V4l<TH>::st((TH*)a.dh + r * a.lddh + g * HD_HID + c, d);
   }
   // block sum of the weight / bias gradient partials, waves added in a fixed order
@@ -224,23 +272,47 @@ static int head_check(const char* name, int h_dt, int64_t rows, int hid, int k, 
   return JMT_OK;
 }
 
-extern "C" int jmt_head_fwd(int h_dt, int y_dt, int64_t rows, int hid, int k, const void* h,
-                            int64_t ldh, const void* w2_0, const void* w2_1, const float* b2_0,
-                            const float* b2_1, void* y_0, void* y_1, int64_t ldy, void* stream) {
-  int rc = head_check("jmt_head_fwd", h_dt, rows, hid, k, h, ldh, w2_0, w2_1);
+// the *_drop entries' mask arguments -> HeadDrop
+static int head_drop_args(const char* name, int64_t rows, float p0, float p1, const uint32_t* ctr,
+                          HeadDrop* dr) {
+  JMT_CHECK_ARG(ctr && ((uintptr_t)ctr & 3) == 0, "%s: null counter block", name);
+  JMT_CHECK_ARG(p0 >= 0.f && p0 < 1.f && p1 >= 0.f && p1 < 1.f, "%s: rates must be in [0, 1)",
+                name);
+  JMT_CHECK_ARG(rows < ((int64_t)1 << 32), "%s: rows = %lld (the counter holds 32 bits of row)",
+                name, (long long)rows);
+  dr->T[0] = dropout_threshold(p0); dr->T[1] = dropout_threshold(p1);
+  dr->s[0] = dropout_scale(p0); dr->s[1] = dropout_scale(p1);
+  dr->ctr = ctr;
+  return JMT_OK;
+}
+
+static int head_fwd_impl(const char* name, int h_dt, int y_dt, int64_t rows, int hid, int k,
+                         const void* h, int64_t ldh, const void* w2_0, const void* w2_1,
+                         const float* b2_0, const float* b2_1, void* y_0, void* y_1, int64_t ldy,
+                         const HeadDrop* drop, void* stream) {
+  int rc = head_check(name, h_dt, rows, hid, k, h, ldh, w2_0, w2_1);
   if (rc != JMT_OK) return rc;
-  JMT_CHECK_ARG(y_dt == JMT_F32 || y_dt == h_dt, "jmt_head_fwd: y dtype");
-  JMT_CHECK_ARG(y_0 && y_1 && ldy >= k, "jmt_head_fwd: outputs");
+  JMT_CHECK_ARG(y_dt == JMT_F32 || y_dt == h_dt, "%s: y dtype", name);
+  JMT_CHECK_ARG(y_0 && y_1 && ldy >= k, "%s: outputs", name);
   if (rows == 0) return JMT_OK;
   HeadArgs a = {};
   a.h = h; a.ldh = ldh; a.w2[0] = w2_0; a.w2[1] = w2_1; a.b2[0] = b2_0; a.b2[1] = b2_1;
   a.y[0] = y_0; a.y[1] = y_1; a.ldy = ldy; a.rows = rows; a.k = k;
+  HeadArgsDrop ad = {};
+  (HeadArgs&)ad = a;
+  if (drop) ad.dr = *drop;
   const dim3 grid(head_blocks(rows));
   hipStream_t st = as_stream(stream);
-#define HFWD(TH, TY)                                                                     \
-  {                                                                                      \
-    if (k == 1) hipLaunchKernelGGL((head_fwd_kernel<TH, TY, 1>), grid, dim3(256), 0, st, a); \
-    else hipLaunchKernelGGL((head_fwd_kernel<TH, TY, HD_KMAX>), grid, dim3(256), 0, st, a); \
+#define HFWD1(TH, TY, K)                                                                   \
+  {                                                                                        \
+    if (drop)                                                                              \
+      hipLaunchKernelGGL((head_fwd_kernel<TH, TY, K, true>), grid, dim3(256), 0, st, ad);  \
+    else hipLaunchKernelGGL((head_fwd_kernel<TH, TY, K, false>), grid, dim3(256), 0, st, a); \
+  }
+#define HFWD(TH, TY)                  \
+  {                                   \
+    if (k == 1) HFWD1(TH, TY, 1)      \
+    else HFWD1(TH, TY, HD_KMAX)       \
   }
   if (h_dt == JMT_BF16) {
     if (y_dt == JMT_F32) HFWD(__bf16, float) else HFWD(__bf16, __bf16)
@@ -248,7 +320,76 @@ extern "C" int jmt_head_fwd(int h_dt, int y_dt, int64_t rows, int hid, int k, co
     if (y_dt == JMT_F32) HFWD(_Float16, float) else HFWD(_Float16, _Float16)
   }
 #undef HFWD
-  JMT_LAUNCH_CHECK("jmt_head_fwd");
+#undef HFWD1
+  JMT_LAUNCH_CHECK(name);
+  return JMT_OK;
+}
+
+extern "C" int jmt_head_fwd(int h_dt, int y_dt, int64_t rows, int hid, int k, const void* h,
+                            int64_t ldh, const void* w2_0, const void* w2_1, const float* b2_0,
+                            const float* b2_1, void* y_0, void* y_1, int64_t ldy, void* stream) {
+  return head_fwd_impl("jmt_head_fwd", h_dt, y_dt, rows, hid, k, h, ldh, w2_0, w2_1, b2_0, b2_1,
+                       y_0, y_1, ldy, nullptr, stream);
+}
+
+extern "C" int jmt_head_fwd_drop(int h_dt, int y_dt, int64_t rows, int hid, int k, const void* h,
+                                 int64_t ldh, const void* w2_0, const void* w2_1,
+                                 const float* b2_0, const float* b2_1, void* y_0, void* y_1,
+                                 int64_t ldy, float p0, float p1, const uint32_t* ctr,
+                                 void* stream) {
+  HeadDrop dr = {};
+  int rc = head_drop_args("jmt_head_fwd_drop", rows, p0, p1, ctr, &dr);
+  if (rc != JMT_OK) return rc;
+  return head_fwd_impl("jmt_head_fwd_drop", h_dt, y_dt, rows, hid, k, h, ldh, w2_0, w2_1, b2_0,
+                       b2_1, y_0, y_1, ldy, &dr, stream);
+}
+
+static int head_bwd_impl(const char* name, int h_dt, int gy_dt, int64_t rows, int hid, int k,
+                         const void* h, int64_t ldh, const void* w2_0, const void* w2_1,
+                         const void* gy_0, const void* gy_1, int64_t ldgy, void* dh, int64_t lddh,
+                         float* dw2_0, float* dw2_1, float* db2_0, float* db2_1, float* partials,
+                         const HeadDrop* drop, void* stream) {
+  int rc = head_check(name, h_dt, rows, hid, k, h, ldh, w2_0, w2_1);
+  if (rc != JMT_OK) return rc;
+  JMT_CHECK_ARG(gy_dt == JMT_F32 || gy_dt == h_dt, "%s: gy dtype", name);
+  JMT_CHECK_ARG(gy_0 && gy_1 && dh && partials && ldgy >= k && lddh % 4 == 0 &&
+                    ((uintptr_t)dh & 7) == 0, "%s: bad gradient buffers", name);
+  if (rows == 0) return JMT_OK;
+  HeadArgs a = {};
+  a.h = h; a.ldh = ldh; a.w2[0] = w2_0; a.w2[1] = w2_1;
+  a.gy[0] = gy_0; a.gy[1] = gy_1; a.ldgy = ldgy; a.dh = dh; a.lddh = lddh;
+  a.partials = partials; a.dw2[0] = dw2_0; a.dw2[1] = dw2_1; a.db2[0] = db2_0; a.db2[1] = db2_1;
+  a.rows = rows; a.k = k;
+  HeadArgsDrop ad = {};
+  (HeadArgs&)ad = a;
+  if (drop) ad.dr = *drop;
+  const int nblk = head_blocks(rows);
+  hipStream_t st = as_stream(stream);
+#define HBWD1(TH, TG, K)                                                                  \
+  {                                                                                       \
+    if (drop)                                                                             \
+      hipLaunchKernelGGL((head_bwd_kernel<TH, TG, K, true>), dim3(nblk), dim3(256), 0, st, ad); \
+    else                                                                                  \
+      hipLaunchKernelGGL((head_bwd_kernel<TH, TG, K, false>), dim3(nblk), dim3(256), 0, st, a); \
+  }
+#define HBWD(TH, TG)                  \
+  {                                   \
+    if (k == 1) HBWD1(TH, TG, 1)      \
+    else HBWD1(TH, TG, HD_KMAX)       \
+  }
+  if (h_dt == JMT_BF16) {
+    if (gy_dt == JMT_F32) HBWD(__bf16, float) else HBWD(__bf16, __bf16)
+  } else {
+    if (gy_dt == JMT_F32) HBWD(_Float16, float) else HBWD(_Float16, _Float16)
+  }
+#undef HBWD
+#undef HBWD1
+  JMT_LAUNCH_CHECK(name);
+  if (dw2_0 || dw2_1 || db2_0 || db2_1) {
+    const int SK = k * (HD_HID + 1);
+    hipLaunchKernelGGL(head_reduce_kernel, dim3((2 * SK + 3) / 4), dim3(256), 0, st, a, nblk);
+    JMT_LAUNCH_CHECK(name);
+  }
   return JMT_OK;
 }
 
@@ -257,35 +398,19 @@ extern "C" int jmt_head_bwd(int h_dt, int gy_dt, int64_t rows, int hid, int k, c
                             const void* gy_1, int64_t ldgy, void* dh, int64_t lddh, float* dw2_0,
                             float* dw2_1, float* db2_0, float* db2_1, float* partials,
                             void* stream) {
-  int rc = head_check("jmt_head_bwd", h_dt, rows, hid, k, h, ldh, w2_0, w2_1);
+  return head_bwd_impl("jmt_head_bwd", h_dt, gy_dt, rows, hid, k, h, ldh, w2_0, w2_1, gy_0, gy_1,
+                       ldgy, dh, lddh, dw2_0, dw2_1, db2_0, db2_1, partials, nullptr, stream);
+}
+
+extern "C" int jmt_head_bwd_drop(int h_dt, int gy_dt, int64_t rows, int hid, int k, const void* h,
+                                 int64_t ldh, const void* w2_0, const void* w2_1,
+                                 const void* gy_0, const void* gy_1, int64_t ldgy, void* dh,
+                                 int64_t lddh, float* dw2_0, float* dw2_1, float* db2_0,
+                                 float* db2_1, float* partials, float p0, float p1,
+                                 const uint32_t* ctr, void* stream) {
+  HeadDrop dr = {};
+  int rc = head_drop_args("jmt_head_bwd_drop", rows, p0, p1, ctr, &dr);
   if (rc != JMT_OK) return rc;
-  JMT_CHECK_ARG(gy_dt == JMT_F32 || gy_dt == h_dt, "jmt_head_bwd: gy dtype");
-  JMT_CHECK_ARG(gy_0 && gy_1 && dh && partials && ldgy >= k && lddh % 4 == 0 &&
-                    ((uintptr_t)dh & 7) == 0, "jmt_head_bwd: bad gradient buffers");
-  if (rows == 0) return JMT_OK;
-  HeadArgs a = {};
-  a.h = h; a.ldh = ldh; a.w2[0] = w2_0; a.w2[1] = w2_1;
-  a.gy[0] = gy_0; a.gy[1] = gy_1; a.ldgy = ldgy; a.dh = dh; a.lddh = lddh;
-  a.partials = partials; a.dw2[0] = dw2_0; a.dw2[1] = dw2_1; a.db2[0] = db2_0; a.db2[1] = db2_1;
-  a.rows = rows; a.k = k;
-  const int nblk = head_blocks(rows);
-  hipStream_t st = as_stream(stream);
-#define HBWD(TH, TG)                                                                          \
-  {                                                                                           \
-    if (k == 1) hipLaunchKernelGGL((head_bwd_kernel<TH, TG, 1>), dim3(nblk), dim3(256), 0, st, a); \
-    else hipLaunchKernelGGL((head_bwd_kernel<TH, TG, HD_KMAX>), dim3(nblk), dim3(256), 0, st, a); \
-  }
-  if (h_dt == JMT_BF16) {
-    if (gy_dt == JMT_F32) HBWD(__bf16, float) else HBWD(__bf16, __bf16)
-  } else {
-    if (gy_dt == JMT_F32) HBWD(_Float16, float) else HBWD(_Float16, _Float16)
-  }
-#undef HBWD
-  JMT_LAUNCH_CHECK("jmt_head_bwd");
-  if (dw2_0 || dw2_1 || db2_0 || db2_1) {
-    const int SK = k * (HD_HID + 1);
-    hipLaunchKernelGGL(head_reduce_kernel, dim3((2 * SK + 3) / 4), dim3(256), 0, st, a, nblk);
-    JMT_LAUNCH_CHECK("jmt_head_bwd(reduce)");
-  }
-  return JMT_OK;
+  return head_bwd_impl("jmt_head_bwd_drop", h_dt, gy_dt, rows, hid, k, h, ldh, w2_0, w2_1, gy_0,
+                       gy_1, ldgy, dh, lddh, dw2_0, dw2_1, db2_0, db2_1, partials, &dr, stream);
 }

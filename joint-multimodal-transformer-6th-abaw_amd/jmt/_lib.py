@@ -159,6 +159,18 @@ _PROTOS = {
     "jmt_head_bwd": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp,
                              c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "jmt_head_bwd_workspace_bytes": (C.c_size_t, [c_i64]),
+    # regressor dropout (csrc/dropout.h): the *_drop head entries are jmt_head_fwd / jmt_head_bwd
+    # + (p0, p1, ctr) before the stream; jmt_dropout_reference is host only (host pointers)
+    "jmt_dropout_next": (c_int, [c_vp, c_vp, c_vp]),
+    "jmt_dropout": (c_int, [c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_f, c_f, c_vp,
+                            c_vp]),
+    "jmt_head_fwd_drop": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_vp, c_vp]),
+    "jmt_head_bwd_drop": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp,
+                                  c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_f, c_f, c_vp, c_vp]),
+    "jmt_dropout_reference": (c_int, [C.POINTER(C.c_uint32), c_i64, c_i64, c_i64, c_f, c_f,
+                                      c_fp]),
     "jmt_ce_stats": (c_int, [c_int, c_i64, c_int, c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp]),
     "jmt_ce_finish": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp]),
     "jmt_ce_bwd": (c_int, [c_int, c_i64, c_int, c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp, c_vp,

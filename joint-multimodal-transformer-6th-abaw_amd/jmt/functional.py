@@ -397,38 +397,106 @@ def linear(xs, W, b=None, r0=0, n=None, out_dtype=None):
     return LinearFn.apply(W, b, r0, n, out_dtype, *xs)
 
 
+# ------------------------------------------------------------------------- regressor dropout
+# The mask of the regressors' dropout (v_dropout / a_dropout) is a function of a per-device state
+# block {seed_lo, seed_hi, call, stream} and the element's (memory row, column) — csrc/dropout.h,
+# DESIGN.md §4.  A forward takes a copy of the block and advances `call` on the device
+# (ops.dropout_next), its backward regenerates the mask from that copy: nothing is stored per
+# element, and a replayed hipGraph draws a new mask per replay.
+_drop_state = {}
+
+
+def _u32(v: int) -> int:
+    v &= 0xFFFFFFFF
+    return v - (1 << 32) if v >= (1 << 31) else v     # the uint32 word as an int32 value
+
+
+def _drop_device(device=None) -> torch.device:
+    d = torch.device("cuda" if device is None else device)
+    return torch.device("cuda", torch.cuda.current_device()) if d.index is None else d
+
+
+def _default_stream_id() -> int:
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def _drop_block(device) -> torch.Tensor:
+    dev = _drop_device(device)
+    st = _drop_state.get(dev)
+    if st is None:
+        seed = torch.initial_seed()
+        st = torch.tensor([_u32(seed), _u32(seed >> 32), 0, _u32(_default_stream_id())],
+                          dtype=torch.int32, device=dev)
+        _drop_state[dev] = st
+    return st
+
+
+def set_dropout_state(seed: int, call: int = 0, stream: Optional[int] = None, device=None):
+    """Set the dropout state block of `device` (default: the current one): the 64-bit seed, the
+    number of masks drawn so far and the stream id (default: the distributed rank, 0 without
+    one).  Restoring what dropout_state() returned resumes the mask sequence of a checkpoint.
+    Off the step: copies to the device; the block keeps its address (captured graphs read it)."""
+    if stream is None:
+        stream = _default_stream_id()
+    st = _drop_block(device)
+    st.copy_(torch.tensor([_u32(seed), _u32(seed >> 32), _u32(call), _u32(stream)],
+                          dtype=torch.int32))
+
+
+def dropout_state(device=None) -> dict:
+    """{"seed", "call", "stream"} of `device`'s dropout state block (synchronises the host)."""
+    w = [int(v) & 0xFFFFFFFF for v in _drop_block(device).cpu().tolist()]
+    return {"seed": w[0] | (w[1] << 32), "call": w[2], "stream": w[3]}
+
+
+def _check_rate(p) -> float:
+    p = float(p or 0.0)
+    if not 0.0 <= p < 1.0:
+        raise JMTError(f"dropout rate {p} outside [0, 1)")
+    return p
+
+
 # ------------------------------------------------------------------------- MLP
 class MLPFn(Function):
-    """y = relu(x W1^T + b1) W2^T + b2, ReLU fused into the first GEMM's epilogue and its
+    """y = drop_p(relu(x W1^T + b1)) W2^T + b2, ReLU fused into the first GEMM's epilogue and its
     backward mask fused into the second GEMM's dgrad epilogue.  The transformer feed-forward
-    (mm_multi_transformers.py:52-56) and the V/A regressors with dropout p=0
-    (two_transformers.py:104-114)."""
+    (mm_multi_transformers.py:52-56, p = 0), one V / A regressor (two_transformers.py:104-114)
+    and the pretrainer's (:131-162).  p > 0: the counter-based mask (csrc/dropout.h) is applied
+    in place to h after the ReLU GEMM and to dh after the masked dgrad (h~ > 0 <=> h > 0 and
+    kept, so the dgrad's mask operand stays right); the W2 gradients read h~."""
 
     @staticmethod
-    def forward(ctx, W1, b1, W2, b2, out_dtype, x):
+    def forward(ctx, W1, b1, W2, b2, out_dtype, x, p=0.0):
         cd = compute_dtype()
         L = Rows(x, cd)
         hid, nout = W1.shape[0], W2.shape[0]
         h = L.like(hid, cd)
         ldh = _ld(h, L.perm)
         _linear_fwd([L.t], L.ld, L.rows, L.F, W1, 0, hid, b1, h, ldh, cd, relu=True)
+        ctr = None
+        if p > 0.0:
+            ctr = ops.dropout_next(_drop_block(h.device))
+            ops.dropout(h, ldh, h, ldh, L.rows, hid, hid, p, p, ctr)
         odt = out_dtype if out_dtype is not None else cd
         y = L.like(nout, odt)
         _linear_fwd([h], ldh, L.rows, hid, W2, 0, nout, b2, y, _ld(y, L.perm), cd)
-        ctx.save_for_backward(W1, b1, W2, b2, L.t, h)
-        ctx.meta = (cd, L, x.dtype, odt)
+        ctx.save_for_backward(W1, b1, W2, b2, L.t, h, ctr)
+        ctx.meta = (cd, L, x.dtype, odt, p)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        W1, b1, W2, b2, xin, h = ctx.saved_tensors
-        cd, L, xdt, odt = ctx.meta
+        W1, b1, W2, b2, xin, h, ctr = ctx.saved_tensors
+        cd, L, xdt, odt, p = ctx.meta
         hid, nout = W1.shape[0], W2.shape[0]
         Gy = _match(gy, Rows(L.like(nout, cd)), cd)
         H = Rows(h)
         dh = L.like(hid, cd)
         ldh = _ld(dh, L.perm)
         _dgrad(Gy, nout, W2, 0, cd, [dh], ldh, 1, hid, aux=h, ldaux=H.ld)
+        if ctr is not None:
+            ops.dropout(dh, ldh, dh, ldh, L.rows, hid, hid, p, p, ctr)
 
         def w2_grads():         # side stream (jmt.streams.run_side)
             if odt == torch.float32 and cd != torch.float32 and nout <= 16:
@@ -461,11 +529,12 @@ class MLPFn(Function):
                 _bgrad(Gh, hid, b1, 0)
 
         streams.run_side(w1_grads, reads=(dh, xin))
-        return None, None, None, None, None, dx
+        return None, None, None, None, None, dx, None
 
 
-def mlp(x, W1, b1, W2, b2, out_dtype=None):
-    return MLPFn.apply(W1, b1, W2, b2, out_dtype, x)
+def mlp(x, W1, b1, W2, b2, out_dtype=None, p=0.0):
+    """p: dropout rate between the ReLU and the second layer (0 = none: nothing is launched)."""
+    return MLPFn.apply(W1, b1, W2, b2, out_dtype, x, _check_rate(p))
 
 
 _pair_mlp = {"on": os.environ.get("JMT_PAIR_MLP", "1") != "0"}
@@ -483,16 +552,19 @@ def set_pair_mlps(on: bool) -> None:
 
 class MLPPairFn(Function):
     """(MLP_a(x), MLP_b(x)) for two same-shaped MLPs on ONE input: the V and A regressors of
-    two_transformers.py:104-114,125-126 (dropout p = 0).  Per output element the arithmetic is
+    two_transformers.py:104-114,125-126.  Per output element the arithmetic is
     MLPFn's, with half the launches: both first layers are one GEMM launch (a 2-entry weight /
     bias table writing [h_a | h_b] side by side), both second layers one launch over the halves
     of h, and in the backward both second-layer input gradients, both second-layer and both
     first-layer weight gradients are one launch each, both first-layer bias gradients one grouped
     column sum; the input gradient is the two dgrads and the same 16-bit add autograd performs
-    for the two uses of x."""
+    for the two uses of x.  Dropout rates (p_a, p_b), either > 0: one state-block copy per call
+    (ops.dropout_next); the fused-head route masks h in registers (the *_drop head kernels, h
+    itself stays unmasked in memory), the GEMM route masks the pair buffer h and then dh in
+    place, one launch each with split = hid (as MLPFn)."""
 
     @staticmethod
-    def forward(ctx, W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, out_dtype, x):
+    def forward(ctx, W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, out_dtype, x, p_a=0.0, p_b=0.0):
         cd = compute_dtype()
         L = Rows(x, cd)
         hid, nout = W1a.shape[0], W2a.shape[0]
@@ -507,7 +579,16 @@ class MLPPairFn(Function):
         odt = out_dtype if out_dtype is not None else cd
         ys = [L.like(nout, odt), L.like(nout, odt)]
         W2c = [weight_as(W2a, cd), weight_as(W2b, cd)]
-        if MLPPairFn._fused_head(cd, hid, nout):
+        fused = MLPPairFn._fused_head(cd, hid, nout)
+        ctr = None
+        if p_a > 0.0 or p_b > 0.0:
+            ctr = ops.dropout_next(_drop_block(h.device))
+            if not fused:
+                ops.dropout(h, ldh, h, ldh, L.rows, 2 * hid, hid, p_a, p_b, ctr)
+        if fused and ctr is not None:
+            ops.head_fwd_drop(h, ldh, L.rows, nout, W2c, (b2a, b2b), ys, _ld(ys[0], L.perm),
+                              p_a, p_b, ctr)
+        elif fused:
             # both second layers as one row kernel over [h_a | h_b] (csrc/head.hip)
             ops.head_fwd(h, ldh, L.rows, nout, W2c, (b2a, b2b), ys, _ld(ys[0], L.perm))
         else:
@@ -517,8 +598,8 @@ class MLPPairFn(Function):
                      b=[w.data_ptr() for w in W2c], ldb=hid, b_kmajor=True, b_mode=1,
                      c=[y.data_ptr() for y in ys], ldc=_ld(ys[0], L.perm), c_mode=1, batch0=2,
                      bias_tab=[b2a, b2b], bias_mode=1, device=h.device)
-        ctx.save_for_backward(W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, L.t, h)
-        ctx.meta = (cd, L, x.dtype, odt)
+        ctx.save_for_backward(W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, L.t, h, ctr)
+        ctx.meta = (cd, L, x.dtype, odt, fused, p_a, p_b)
         return ys[0], ys[1]
 
     @staticmethod
@@ -553,8 +634,8 @@ class MLPPairFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gya, gyb):
-        W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, xin, h = ctx.saved_tensors
-        cd, L, xdt, odt = ctx.meta
+        W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, xin, h, ctr = ctx.saved_tensors
+        cd, L, xdt, odt, fused, p_a, p_b = ctx.meta
         hid, nout = W1a.shape[0], W2a.shape[0]
         dev = h.device
         ldh = _ld(h, L.perm)
@@ -566,7 +647,7 @@ class MLPPairFn(Function):
             if gy is None:
                 gy = torch.zeros(L.like(nout, odt).shape, dtype=odt, device=dev)
             gys.append(gy)
-        if MLPPairFn._fused_head(cd, hid, nout):
+        if fused:       # (the route the forward took: with dropout, h is masked only off it)
             # dh (ReLU-masked) and both output layers' weight / bias gradients in one row
             # kernel from the fp32 loss gradient (csrc/head.hip), then the input gradient as ONE
             # K-concatenated GEMM dx = [dh_a | dh_b] [W1a; W1b] (one rounding of the sum of both
@@ -578,8 +659,12 @@ class MLPPairFn(Function):
             W2c = [weight_as(W2a, cd), weight_as(W2b, cd)]
             dw2 = [_grad_buffer(W2a), _grad_buffer(W2b)]
             db2 = [_grad_buffer(b2a), _grad_buffer(b2b)]
-            ops.head_bwd(h, ldh, L.rows, nout, W2c, [G.t for G in G2], G2[0].ld, dh, ldh, dw2,
-                         db2)
+            if ctr is not None:
+                ops.head_bwd_drop(h, ldh, L.rows, nout, W2c, [G.t for G in G2], G2[0].ld, dh,
+                                  ldh, dw2, db2, p_a, p_b, ctr)
+            else:
+                ops.head_bwd(h, ldh, L.rows, nout, W2c, [G.t for G in G2], G2[0].ld, dh, ldh,
+                             dw2, db2)
             _grad_done(W2a, W2b, b2a, b2b)
             dx = None
             if ctx.needs_input_grad[9]:
@@ -594,7 +679,7 @@ class MLPPairFn(Function):
             streams.run_side(lambda: MLPPairFn._w1_grads(dh, ldh, xin, L, hid, cd, dev,
                                                          (W1a, W1b), (b1a, b1b)),
                              reads=(dh, xin))
-            return (None,) * 9 + (dx,)
+            return (None,) * 9 + (dx, None, None)
         Gys = [_match(gy, Rows(L.like(nout, cd)), cd) for gy in gys]
         if nout == 1 or Gys[0].ld == Gys[1].ld:
             # both second-layer input gradients (ReLU-masked) in one launch into [dh_a | dh_b]
@@ -608,6 +693,8 @@ class MLPPairFn(Function):
         else:
             for Gy, W2, hp, dhp in zip(Gys, (W2a, W2b), hs, dhs):
                 _dgrad(Gy, nout, W2, 0, cd, [dhp], ldh, 1, hid, aux=hp, ldaux=ldh)
+        if ctr is not None:
+            ops.dropout(dh, ldh, dh, ldh, L.rows, 2 * hid, hid, p_a, p_b, ctr)
 
         def w2_grads():         # side stream (jmt.streams.run_side), as in MLPFn
             if odt == torch.float32 and cd != torch.float32 and nout <= 16:
@@ -637,7 +724,7 @@ class MLPPairFn(Function):
         streams.run_side(lambda: MLPPairFn._w1_grads(dh, ldh, xin, L, hid, cd, dev, (W1a, W1b),
                                                      (b1a, b1b)),
                          reads=(dh, xin))
-        return (None,) * 9 + (dx,)
+        return (None,) * 9 + (dx, None, None)
 
     @staticmethod
     def _w1_grads(dh, ldh, xin, L, hid, cd, dev, W1s, b1s):
@@ -665,12 +752,14 @@ class MLPPairFn(Function):
         _grad_done(*b1s)
 
 
-def mlp_pair(x, mlp_a, mlp_b, out_dtype=None):
-    """Both regressor MLPs (jmt.nn.MLP: Linear, ReLU, [Dropout p=0], Linear) on the same x."""
+def mlp_pair(x, mlp_a, mlp_b, out_dtype=None, p=(0.0, 0.0)):
+    """Both regressor MLPs (jmt.nn.MLP: Linear, ReLU, [Dropout], Linear) on the same x; p: the
+    two dropout rates in effect (0 in eval)."""
     la1, la2 = mlp_a[0], mlp_a[len(mlp_a) - 1]
     lb1, lb2 = mlp_b[0], mlp_b[len(mlp_b) - 1]
     return MLPPairFn.apply(la1.weight, la1.bias, la2.weight, la2.bias, lb1.weight, lb1.bias,
-                           lb2.weight, lb2.bias, out_dtype, x)
+                           lb2.weight, lb2.bias, out_dtype, x, _check_rate(p[0]),
+                           _check_rate(p[1]))
 
 
 # ------------------------------------------------------------------------- L2 normalize

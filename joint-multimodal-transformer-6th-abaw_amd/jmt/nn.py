@@ -90,7 +90,9 @@ class MultiheadAttention(nn.Module):
 
 class MLP(nn.Sequential):
     """Linear-ReLU-[Dropout]-Linear with nn.Sequential indexing (so keys read
-    `feed_forward.0.weight` / `vregressor.3.weight`), executed as one fused MLP function."""
+    `feed_forward.0.weight` / `vregressor.3.weight`), executed as one fused MLP function; the
+    nn.Dropout entry only holds its place in the indexing: the rate goes to the HIP mask
+    (jmt.functional, csrc/dropout.h)."""
 
     def __init__(self, d_in: int, d_hidden: int, d_out: int, dropout=None):
         mods = [Linear(d_in, d_hidden), nn.ReLU()]
@@ -102,8 +104,9 @@ class MLP(nn.Sequential):
 
     def forward(self, x, out_dtype=None):
         l1, l2 = self[0], self[len(self) - 1]
-        if self._p and self.training:
-            # dropout p > 0 is off the benchmarked path (config_file.json:69-70 use 0.0)
-            h = torch.nn.functional.dropout(l1(x).relu(), self._p, True)
-            return l2(h, out_dtype=out_dtype)
-        return F.mlp(x, l1.weight, l1.bias, l2.weight, l2.bias, out_dtype=out_dtype)
+        return F.mlp(x, l1.weight, l1.bias, l2.weight, l2.bias, out_dtype=out_dtype,
+                     p=self.drop_rate())
+
+    def drop_rate(self) -> float:
+        """The dropout rate in effect: the constructor's while training, 0 in eval."""
+        return float(self._p or 0.0) if self.training else 0.0

@@ -779,6 +779,55 @@ def head_bwd(h, ldh, rows, k, w2, gys, ldgy, dh, lddh, dw2, db2):
               stream())
 
 
+# ------------------------------------------------------------------------------------ dropout
+# Counter-based regressor dropout (csrc/dropout.h).  State blocks and counters are 4-element
+# int32 tensors holding the uint32 words {seed_lo, seed_hi, call, stream}.
+
+def dropout_next(state: torch.Tensor) -> torch.Tensor:
+    """A fresh copy of the state block for one forward / backward pair; state.call += 1."""
+    _require_cuda(state)
+    out = torch.empty(4, dtype=torch.int32, device=state.device)
+    _lib.call("jmt_dropout_next", state.data_ptr(), out.data_ptr(), stream())
+    return out
+
+
+def dropout(x, ldx, y, ldy, rows, cols, split, p0, p1, ctr):
+    """y = m . x over (rows x cols) (jmt_dropout; y may be x); columns < split use p0."""
+    _require_cuda(x, y, ctr)
+    _lib.call("jmt_dropout", dt(x), x.data_ptr(), ldx, y.data_ptr(), ldy, rows, cols, split,
+              float(p0), float(p1), ctr.data_ptr(), stream())
+
+
+def dropout_reference(ctr, rows, cols, split, p0, p1):
+    """Host only: the (rows, cols) fp32 multipliers of state block `ctr` (4 ints) as a numpy
+    array (jmt_dropout_reference)."""
+    import numpy as np
+    words = (C.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in ctr])
+    out = np.empty((rows, cols), dtype=np.float32)
+    _lib.call("jmt_dropout_reference", words, rows, cols, split, float(p0), float(p1),
+              out.ctypes.data_as(_lib.c_fp))
+    return out
+
+
+def head_fwd_drop(h, ldh, rows, k, w2, b2, ys, ldy, p0, p1, ctr):
+    """head_fwd on the dropout-masked hidden activations (jmt_head_fwd_drop)."""
+    p = lambda t: t.data_ptr() if t is not None else None
+    _lib.call("jmt_head_fwd_drop", dt(h), dt(ys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
+              w2[0].data_ptr(), w2[1].data_ptr(), p(b2[0]), p(b2[1]), ys[0].data_ptr(),
+              ys[1].data_ptr(), ldy, float(p0), float(p1), ctr.data_ptr(), stream())
+
+
+def head_bwd_drop(h, ldh, rows, k, w2, gys, ldgy, dh, lddh, dw2, db2, p0, p1, ctr):
+    """head_bwd with the forward's mask regenerated from `ctr` (jmt_head_bwd_drop)."""
+    p = lambda t: t.data_ptr() if t is not None else None
+    nbytes = _lib.load().jmt_head_bwd_workspace_bytes(rows)
+    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=h.device)
+    _lib.call("jmt_head_bwd_drop", dt(h), dt(gys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
+              w2[0].data_ptr(), w2[1].data_ptr(), gys[0].data_ptr(), gys[1].data_ptr(), ldgy,
+              dh.data_ptr(), lddh, p(dw2[0]), p(dw2[1]), p(db2[0]), p(db2[1]), ws.data_ptr(),
+              float(p0), float(p1), ctr.data_ptr(), stream())
+
+
 def ce_stats(x, label, k, lo, hi, weights, stats):
     n = x.numel() // k
     _lib.call("jmt_ce_stats", dt(x), n, k, x.data_ptr(), label.data_ptr(), lo, hi,

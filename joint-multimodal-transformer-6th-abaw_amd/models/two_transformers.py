@@ -87,11 +87,12 @@ class Two_transformers(nn.Module):
                     self.output_format == 'FC')
         # regressors in fp32 out (predictions feed the fp32 CCC statistics)
         vr, ar = self.vregressor, self.aregressor
-        if (F.pair_mlps_enabled() and not ((vr._p or ar._p) and self.training)
-                and vr[0].weight.shape == ar[0].weight.shape):
+        if F.pair_mlps_enabled() and vr[0].weight.shape == ar[0].weight.shape:
             # both regressors read av: one MLP-pair function (fewer launches, same arithmetic
-            # per output element as the two MLP calls below)
-            vouts, aouts = F.mlp_pair(av, vr, ar, out_dtype=torch.float32)
+            # per output element as the two MLP calls below; v_dropout / a_dropout mask the two
+            # halves of its hidden buffer)
+            vouts, aouts = F.mlp_pair(av, vr, ar, out_dtype=torch.float32,
+                                      p=(vr.drop_rate(), ar.drop_rate()))
             vouts, aouts = vouts.squeeze(2), aouts.squeeze(2)
         else:
             vouts = vr(av, out_dtype=torch.float32).squeeze(2)
