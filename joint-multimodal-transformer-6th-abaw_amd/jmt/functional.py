@@ -26,6 +26,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
+from . import linear_gemm as lg
 from . import ops
 from . import streams
 from ._lib import F32, JMTError
@@ -193,6 +194,10 @@ class Rows:
             inv[d] = i
         return y.permute(*inv, len(self.perm))
 
+    def op(self) -> "lg.Operand":
+        """The rows as one GEMM operand."""
+        return lg.strided(self.t, self.ld)
+
     def same_rows(self, other: "Rows") -> bool:
         return self.perm == other.perm and self.shape[:-1] == other.shape[:-1]
 
@@ -210,6 +215,11 @@ def _cast_keep_layout(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 def _ld(y: torch.Tensor, perm) -> int:
     dims = [d for d in perm if y.shape[d] != 1]
     return y.stride(dims[-1]) if dims else max(y.shape[-1], 1)
+
+
+def _out(y: torch.Tensor, perm) -> "lg.Operand":
+    """A tensor made by Rows.like as one GEMM operand."""
+    return lg.strided(y, _ld(y, perm))
 
 
 def _ptr(t: torch.Tensor, elem_off: int = 0) -> int:
@@ -230,45 +240,7 @@ def _dc(d: torch.dtype) -> int:
     return ops.dt(d)
 
 
-# ------------------------------------------------------------------------- GEMM helpers
-def _linear_fwd(xin, ld_in, rows, kseg, W, r0, n, b, y, ldy, cd, relu=False):
-    Wc = weight_as(W, cd)
-    nseg = len(xin)
-    ops.gemm(M=rows, N=n, K=kseg * nseg, ab_dtype=_dc(cd), c_dtype=_dc(y.dtype),
-             a=[x.data_ptr() for x in xin], lda=ld_in if rows > 1 else _vec(cd), a_kmajor=True,
-             a_mode=2 if nseg > 1 else 0, a_kseg=kseg if nseg > 1 else 0,
-             b=[_ptr(Wc, r0 * Wc.shape[1])], ldb=Wc.shape[1], b_kmajor=True,
-             c=[y.data_ptr()], ldc=ldy,
-             bias=b[r0:r0 + n] if b is not None else None, bias_mode=1, relu=relu,
-             device=y.device)
-
-
-def _dgrad(G: Rows, n, W, r0, cd, outs, ld_out, nseg, kseg, aux=None, ldaux=0, beta=0.0):
-    """outs[s] = (dY . W[r0:r0+n, s*kseg:(s+1)*kseg]) (masked by aux > 0; beta = 1 adds to the
-    existing outs)."""
-    Wc = weight_as(W, cd)
-    Kin = Wc.shape[1]
-    if n == 1:   # dY is a column: read it as an MN-major operand (row stride irrelevant)
-        a_ld, a_kmaj = _vec(cd), False
-    else:
-        a_ld, a_kmaj = G.ld, True
-    ops.gemm(M=G.rows, N=kseg, K=n, ab_dtype=_dc(cd), c_dtype=_dc(outs[0].dtype),
-             a=[G.t.data_ptr()], lda=a_ld, a_kmajor=a_kmaj,
-             b=[_ptr(Wc, r0 * Kin)], ldb=Kin, b_kmajor=False,
-             c=[o.data_ptr() for o in outs], ldc=ld_out, c_mode=1 if nseg > 1 else 0,
-             batch0=nseg, sA=(0, 0), sB=(kseg, 0), sC=(0, 0), beta=beta,
-             aux=aux, ldaux=ldaux, device=G.t.device)
-
-
-_fused_bgrad = {"on": os.environ.get("JMT_FUSED_BGRAD", "1") != "0"}
-
-
-def fused_bgrad_ok(cd) -> bool:
-    """Bias gradients as the A row sums of their weight-gradient GEMM (jmt_gemm_desc.dbias_tab,
-    16-bit operands only); JMT_FUSED_BGRAD=0 keeps the separate column-sum launches."""
-    return _fused_bgrad["on"] and cd in (torch.bfloat16, torch.float16)
-
-
+# ------------------------------------------------------------------------- weight-gradient queue
 def wgrad_group_ok() -> bool:
     """Whether weight-gradient launches may be queued and flushed grouped (ops.wgrad_scope /
     defer): not under a GradBucketer, whose buckets complete in the profiled launch order."""
@@ -289,49 +261,6 @@ def wgrad_scope(cd=torch.float32):
     wgrad_defer_ok(cd)), else a no-op context."""
     return ops.wgrad_scope(defer=wgrad_defer_ok(cd)) if wgrad_group_ok() else \
         contextlib.nullcontext()
-
-
-def _wgrad(G: Rows, n, xin, ld_in, kseg, W, r0, cd, b=None, defer: bool = False) -> bool:
-    """W.grad[r0:r0+n, s*kseg:...] += dY^T X_s   (split-K over the rows); with `b`, also
-    b.grad[r0:r0+n] += the column sums of dY inside the same GEMM when the launch form allows it
-    (n > 1, 16-bit; K segments share dY, so only segment 0 sums it).  Returns True when b.grad
-    was written.  defer: the launch may wait for the end of the backward pass to be flushed with
-    the other deferred weight gradients as one grouped launch — only for callers after which
-    nothing writes dY or the inputs again."""
-    gW = _grad_buffer(W)
-    if gW is None:
-        return False
-    nseg = len(xin)
-    Kin = W.shape[1]
-    dbt = None
-    if b is not None and n > 1 and fused_bgrad_ok(cd):
-        gb = _grad_buffer(b)
-        if gb is not None:
-            dbt = [gb[r0:r0 + n]] + [None] * (nseg - 1)
-
-    def done():
-        _grad_done(W)
-        if dbt is not None:
-            _grad_done(b)
-
-    # A = dY^T (MN-major); for n == 1 the single row is the contiguous dY column (K-major)
-    a_ld, a_kmaj = (G.ld, False) if n > 1 else (_vec(cd), True)
-    ops.gemm(M=n, N=kseg, K=G.rows, ab_dtype=_dc(cd), c_dtype=F32,
-             a=[G.t.data_ptr()], lda=a_ld, a_kmajor=a_kmaj,
-             b=[x.data_ptr() for x in xin], ldb=ld_in, b_kmajor=False,
-             b_mode=1 if nseg > 1 else 0,
-             c=[_ptr(gW, r0 * Kin)], ldc=Kin, batch0=nseg, sA=(0, 0), sB=(0, 0),
-             sC=(kseg, 0), beta=1.0, dbias_tab=dbt, device=G.t.device,
-             done=done, keep=(G.t, gW, *xin, *(dbt or ())),
-             defer=defer if wgrad_group_ok() else False)
-    return dbt is not None
-
-
-def _bgrad(G: Rows, n, b, r0):
-    gb = _grad_buffer(b)
-    if gb is not None:
-        ops.colsum(G.t, G.ld, G.rows, n, gb[r0:r0 + n], beta_acc=True)
-        _grad_done(b)
 
 
 # ------------------------------------------------------------------------- Linear
@@ -357,7 +286,7 @@ class LinearFn(Function):
         odt = out_dtype if out_dtype is not None else cd
         y = L0.like(n, odt)
         xin = [l.t for l in lay]
-        _linear_fwd(xin, L0.ld, L0.rows, kseg, W, r0, n, b, y, _ld(y, L0.perm), cd)
+        lg.fwd(lg.kcat(xin, L0.ld, kseg), L0.rows, W, b, _out(y, L0.perm), cd, r0, n)
         ctx.save_for_backward(W, b, *xin)
         ctx.meta = (r0, n, cd, L0, kseg, [x.dtype for x in xs])
         return y
@@ -373,7 +302,7 @@ class LinearFn(Function):
         need = [ctx.needs_input_grad[5 + i] for i in range(nseg)]
         if any(need):
             outs = [L0.like(kseg, cd) for _ in range(nseg)]
-            _dgrad(Gy, n, W, r0, cd, outs, _ld(outs[0], L0.perm), nseg, kseg)
+            lg.dgrad(Gy.op(), Gy.rows, n, W, lg.table(outs, _ld(outs[0], L0.perm)), cd, r0, kseg)
             for i in range(nseg):
                 if need[i]:
                     dxs[i] = outs[i] if in_dtypes[i] == cd else _cast_keep_layout(outs[i],
@@ -382,8 +311,8 @@ class LinearFn(Function):
         def param_grads():      # side stream (jmt.streams.run_side)
             # no input gradient: nothing runs behind this node that could write gy or the
             # saved inputs, so the launch may join the end-of-backward group
-            if not _wgrad(Gy, n, xin, L0.ld, kseg, W, r0, cd, b, defer=not any(need)):
-                _bgrad(Gy, n, b, r0)
+            lg.wgrad(Gy.op(), lg.table(xin, L0.ld), Gy.rows, n, W, cd, b, r0, kseg,
+                     defer=not any(need))
 
         streams.run_side(param_grads, reads=(Gy.t,) + tuple(xin))
         return (None, None, None, None, None, *dxs)
@@ -473,14 +402,14 @@ class MLPFn(Function):
         hid, nout = W1.shape[0], W2.shape[0]
         h = L.like(hid, cd)
         ldh = _ld(h, L.perm)
-        _linear_fwd([L.t], L.ld, L.rows, L.F, W1, 0, hid, b1, h, ldh, cd, relu=True)
+        lg.fwd(L.op(), L.rows, W1, b1, lg.strided(h, ldh), cd, relu=True)
         ctr = None
         if p > 0.0:
             ctr = ops.dropout_next(_drop_block(h.device))
             ops.dropout(h, ldh, h, ldh, L.rows, hid, hid, p, p, ctr)
         odt = out_dtype if out_dtype is not None else cd
         y = L.like(nout, odt)
-        _linear_fwd([h], ldh, L.rows, hid, W2, 0, nout, b2, y, _ld(y, L.perm), cd)
+        lg.fwd(lg.strided(h, ldh), L.rows, W2, b2, _out(y, L.perm), cd)
         ctx.save_for_backward(W1, b1, W2, b2, L.t, h, ctr)
         ctx.meta = (cd, L, x.dtype, odt, p)
         return y
@@ -494,7 +423,7 @@ class MLPFn(Function):
         H = Rows(h)
         dh = L.like(hid, cd)
         ldh = _ld(dh, L.perm)
-        _dgrad(Gy, nout, W2, 0, cd, [dh], ldh, 1, hid, aux=h, ldaux=H.ld)
+        lg.dgrad(Gy.op(), Gy.rows, nout, W2, lg.strided(dh, ldh), cd, aux=h, ldaux=H.ld)
         if ctr is not None:
             ops.dropout(dh, ldh, dh, ldh, L.rows, hid, hid, p, p, ctr)
 
@@ -506,27 +435,24 @@ class MLPFn(Function):
                 # rounded copy would cost up to ~20 % relative error, so they are reduced from
                 # fp32 dY and an fp32 copy of the (small) hidden activations with the exact-f32
                 # MFMA GEMM.
-                G32 = _match(gy, Rows(L.like(nout, torch.float32)), torch.float32)
-                h32 = _cast_keep_layout(h, torch.float32)
-                H32 = Rows(h32)
-                _wgrad(G32, nout, [H32.t], H32.ld, hid, W2, 0, torch.float32)
-                _bgrad(G32, nout, b2, 0)
+                G = _match(gy, Rows(L.like(nout, torch.float32)), torch.float32)
+                hx, dt = Rows(_cast_keep_layout(h, torch.float32)), torch.float32
             else:
-                _wgrad(Gy, nout, [h], H.ld, hid, W2, 0, cd)
-                _bgrad(Gy, nout, b2, 0)
+                G, hx, dt = Gy, H, cd
+            lg.wgrad(G.op(), hx.op(), G.rows, nout, W2, dt)
+            lg.bias_grad(G.op(), G.rows, nout, [b2])
 
         streams.run_side(w2_grads, reads=(gy, Gy.t, h))
         Gh = Rows(dh)
         dx = None
         if ctx.needs_input_grad[5]:
             dx = L.like(L.F, cd)
-            _dgrad(Gh, hid, W1, 0, cd, [dx], _ld(dx, L.perm), 1, L.F)
+            lg.dgrad(Gh.op(), Gh.rows, hid, W1, _out(dx, L.perm), cd)
             if xdt != cd:
                 dx = _cast_keep_layout(dx, xdt)
 
         def w1_grads():
-            if not _wgrad(Gh, hid, [xin], L.ld, L.F, W1, 0, cd, b1):
-                _bgrad(Gh, hid, b1, 0)
+            lg.wgrad(Gh.op(), lg.strided(xin, L.ld), Gh.rows, hid, W1, cd, b1)
 
         streams.run_side(w1_grads, reads=(dh, xin))
         return None, None, None, None, None, dx, None
@@ -570,16 +496,12 @@ class MLPPairFn(Function):
         hid, nout = W1a.shape[0], W2a.shape[0]
         h = L.like(2 * hid, cd)
         ldh = _ld(h, L.perm)
-        Wa, Wb = weight_as(W1a, cd), weight_as(W1b, cd)
-        ops.gemm(M=L.rows, N=hid, K=L.F, ab_dtype=_dc(cd), c_dtype=_dc(cd),
-                 a=[L.t.data_ptr()], lda=L.ld, a_kmajor=True,
-                 b=[Wa.data_ptr(), Wb.data_ptr()], ldb=L.F, b_kmajor=True, b_mode=1,
-                 c=[h.data_ptr()], ldc=ldh, batch0=2, sA=(0, 0), sC=(hid, 0),
-                 bias_tab=[b1a, b1b], bias_mode=1, relu=True, device=h.device)
+        # both first layers: one launch writing [h_a | h_b] side by side
+        lg.fwd(L.op(), L.rows, (W1a, W1b), (b1a, b1b), lg.strided(h, ldh, hid), cd, relu=True)
         odt = out_dtype if out_dtype is not None else cd
         ys = [L.like(nout, odt), L.like(nout, odt)]
-        W2c = [weight_as(W2a, cd), weight_as(W2b, cd)]
         fused = MLPPairFn._fused_head(cd, hid, nout)
+        W2c = [weight_as(W2a, cd), weight_as(W2b, cd)] if fused else None
         ctr = None
         if p_a > 0.0 or p_b > 0.0:
             ctr = ops.dropout_next(_drop_block(h.device))
@@ -593,11 +515,8 @@ class MLPPairFn(Function):
             ops.head_fwd(h, ldh, L.rows, nout, W2c, (b2a, b2b), ys, _ld(ys[0], L.perm))
         else:
             # both second layers: one GEMM launch over the halves of h (2-entry tables)
-            ops.gemm(M=L.rows, N=nout, K=hid, ab_dtype=_dc(cd), c_dtype=_dc(odt),
-                     a=[h.data_ptr()], lda=ldh, a_kmajor=True, sA=(hid, 0),
-                     b=[w.data_ptr() for w in W2c], ldb=hid, b_kmajor=True, b_mode=1,
-                     c=[y.data_ptr() for y in ys], ldc=_ld(ys[0], L.perm), c_mode=1, batch0=2,
-                     bias_tab=[b2a, b2b], bias_mode=1, device=h.device)
+            lg.fwd(lg.strided(h, ldh, hid), L.rows, (W2a, W2b), (b2a, b2b),
+                   lg.table(ys, _ld(ys[0], L.perm)), cd)
         ctx.save_for_backward(W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, L.t, h, ctr)
         ctx.meta = (cd, L, x.dtype, odt, fused, p_a, p_b)
         return ys[0], ys[1]
@@ -611,25 +530,18 @@ class MLPPairFn(Function):
                 nout <= ops.HEAD_KMAX)
 
     @staticmethod
-    def _w2_grads(Gs, hh, ldhh, hid, nout, W2s, b2s, dt, dev):
-        """W2_g.grad += G_g^T h_g (both in one launch when the gradients share a row stride),
-        b2_g.grad += column sums of G_g."""
-        gWs = [_grad_buffer(W) for W in W2s]
-        if nout == 1 or Gs[0].ld == Gs[1].ld:
-            a_ld, a_kmaj = (Gs[0].ld, False) if nout > 1 else (_vec(dt), True)
-            if all(g is not None for g in gWs):
-                ops.gemm(M=nout, N=hid, K=Gs[0].rows, ab_dtype=_dc(dt), c_dtype=F32,
-                         a=[G.t.data_ptr() for G in Gs], lda=a_ld, a_kmajor=a_kmaj, a_mode=1,
-                         b=[hh.data_ptr()], ldb=ldhh, b_kmajor=False, sB=(hid, 0),
-                         c=[g.data_ptr() for g in gWs], ldc=hid, c_mode=1, batch0=2, beta=1.0,
-                         device=dev)
-                _grad_done(*W2s)
-                gWs = None
-        if gWs is not None:
+    def _w2_grads(Gs, hh, ldhh, hid, nout, W2s, b2s, dt):
+        """W2_g.grad += G_g^T h_g (both in one launch when the gradients share a row stride and
+        neither weight is frozen), b2_g.grad += column sums of G_g."""
+        if (nout == 1 or Gs[0].ld == Gs[1].ld) and all(W.requires_grad for W in W2s):
+            lg.wgrad(lg.table([G.t for G in Gs], Gs[0].ld), lg.strided(hh, ldhh, hid),
+                     Gs[0].rows, nout, W2s, dt, queue=False)
+        else:
             for half, (G, W2) in enumerate(zip(Gs, W2s)):
-                _wgrad(G, nout, [hh[..., half * hid:(half + 1) * hid]], ldhh, hid, W2, 0, dt)
+                lg.wgrad(G.op(), lg.strided(hh[..., half * hid:(half + 1) * hid], ldhh), G.rows,
+                         nout, W2, dt)
         for G, b2 in zip(Gs, b2s):
-            _bgrad(G, nout, b2, 0)
+            lg.bias_grad(G.op(), G.rows, nout, [b2])
 
     @staticmethod
     @once_differentiable
@@ -642,6 +554,11 @@ class MLPPairFn(Function):
         hs = (h[..., :hid], h[..., hid:])
         dh = L.like(2 * hid, cd)
         dhs = (dh[..., :hid], dh[..., hid:])
+
+        def w1_grads():         # one batched launch (+ one grouped column-sum launch pair)
+            lg.wgrad(lg.strided(dh, ldh, hid), lg.strided(xin, L.ld), L.rows, hid, (W1a, W1b),
+                     cd, (b1a, b1b), queue=False)
+
         gys = []
         for gy in (gya, gyb):
             if gy is None:
@@ -670,29 +587,20 @@ class MLPPairFn(Function):
             if ctx.needs_input_grad[9]:
                 dx = L.like(L.F, cd)
                 W1c = [weight_as(W1a, cd), weight_as(W1b, cd)]
-                ops.gemm(M=L.rows, N=L.F, K=2 * hid, ab_dtype=_dc(cd), c_dtype=_dc(cd),
-                         a=[dh.data_ptr()], lda=ldh, a_kmajor=True,
-                         b=[w.data_ptr() for w in W1c], ldb=L.F, b_kmajor=False, b_mode=2,
-                         b_kseg=hid, c=[dx.data_ptr()], ldc=_ld(dx, L.perm), device=dev)
+                lg.dgrad(lg.strided(dh, ldh), L.rows, 2 * hid, lg.kcat(W1c, L.F, hid),
+                         _out(dx, L.perm), cd)
                 if xdt != cd:
                     dx = _cast_keep_layout(dx, xdt)
-            streams.run_side(lambda: MLPPairFn._w1_grads(dh, ldh, xin, L, hid, cd, dev,
-                                                         (W1a, W1b), (b1a, b1b)),
-                             reads=(dh, xin))
+            streams.run_side(w1_grads, reads=(dh, xin))
             return (None,) * 9 + (dx, None, None)
         Gys = [_match(gy, Rows(L.like(nout, cd)), cd) for gy in gys]
         if nout == 1 or Gys[0].ld == Gys[1].ld:
             # both second-layer input gradients (ReLU-masked) in one launch into [dh_a | dh_b]
-            a_ld, a_kmaj = (_vec(cd), False) if nout == 1 else (Gys[0].ld, True)
-            W2c = [weight_as(W2a, cd), weight_as(W2b, cd)]
-            ops.gemm(M=L.rows, N=hid, K=nout, ab_dtype=_dc(cd), c_dtype=_dc(cd),
-                     a=[G.t.data_ptr() for G in Gys], lda=a_ld, a_kmajor=a_kmaj, a_mode=1,
-                     b=[w.data_ptr() for w in W2c], ldb=hid, b_kmajor=False, b_mode=1,
-                     c=[dh.data_ptr()], ldc=ldh, batch0=2, sC=(hid, 0), aux=h, ldaux=ldh,
-                     device=dev)
+            lg.dgrad(lg.table([G.t for G in Gys], Gys[0].ld), L.rows, nout, (W2a, W2b),
+                     lg.strided(dh, ldh, hid), cd, aux=h, ldaux=ldh)
         else:
             for Gy, W2, hp, dhp in zip(Gys, (W2a, W2b), hs, dhs):
-                _dgrad(Gy, nout, W2, 0, cd, [dhp], ldh, 1, hid, aux=hp, ldaux=ldh)
+                lg.dgrad(Gy.op(), Gy.rows, nout, W2, lg.strided(dhp, ldh), cd, aux=hp, ldaux=ldh)
         if ctr is not None:
             ops.dropout(dh, ldh, dh, ldh, L.rows, 2 * hid, hid, p_a, p_b, ctr)
 
@@ -702,18 +610,18 @@ class MLPPairFn(Function):
                 G32 = [_match(gy, Rows(L.like(nout, torch.float32)), torch.float32)
                        for gy in gys]
                 MLPPairFn._w2_grads(G32, h32, _ld(h32, L.perm), hid, nout, (W2a, W2b),
-                                    (b2a, b2b), torch.float32, dev)
+                                    (b2a, b2b), torch.float32)
             else:
-                MLPPairFn._w2_grads(Gys, h, ldh, hid, nout, (W2a, W2b), (b2a, b2b), cd, dev)
+                MLPPairFn._w2_grads(Gys, h, ldh, hid, nout, (W2a, W2b), (b2a, b2b), cd)
 
         streams.run_side(w2_grads, reads=tuple(gys) + (h,) + tuple(G.t for G in Gys))
         dx = None
         if ctx.needs_input_grad[9]:
             dx = L.like(L.F, cd)
-            ldx = _ld(dx, L.perm)
             dxb = L.like(L.F, cd)
-            _dgrad(Rows(dhs[0]), hid, W1a, 0, cd, [dx], ldx, 1, L.F)
-            _dgrad(Rows(dhs[1]), hid, W1b, 0, cd, [dxb], _ld(dxb, L.perm), 1, L.F)
+            for dhp, W1, o in zip(dhs, (W1a, W1b), (dx, dxb)):
+                Gh = Rows(dhp)
+                lg.dgrad(Gh.op(), Gh.rows, hid, W1, _out(o, L.perm), cd)
             # the sum of the two input gradients rounded as autograd rounds it (a beta = 1
             # accumulate in the second dgrad saves this add but rounds once less, which moved an
             # fp16 gradient of the H8/L2 golden case 0.02 % past the error model's bound)
@@ -721,35 +629,8 @@ class MLPPairFn(Function):
             if xdt != cd:
                 dx = _cast_keep_layout(dx, xdt)
 
-        streams.run_side(lambda: MLPPairFn._w1_grads(dh, ldh, xin, L, hid, cd, dev, (W1a, W1b),
-                                                     (b1a, b1b)),
-                         reads=(dh, xin))
+        streams.run_side(w1_grads, reads=(dh, xin))
         return (None,) * 9 + (dx, None, None)
-
-    @staticmethod
-    def _w1_grads(dh, ldh, xin, L, hid, cd, dev, W1s, b1s):
-        """One grouped wgrad launch + one grouped column-sum launch pair (side stream)."""
-        gws = []
-        for W in W1s:
-            g = _grad_buffer(W)
-            gws.append(g if g is not None else torch.zeros_like(W))
-        dbs = []
-        for b in b1s:
-            gb = _grad_buffer(b)
-            dbs.append(gb if gb is not None else torch.empty(hid, dtype=torch.float32,
-                                                             device=dev))
-        fuse = hid > 1 and fused_bgrad_ok(cd)      # bias sums as the wgrad's A row sums
-        ops.gemm(M=hid, N=L.F, K=L.rows, ab_dtype=_dc(cd), c_dtype=F32,
-                 a=[dh.data_ptr()], lda=ldh, a_kmajor=False,
-                 b=[xin.data_ptr()], ldb=L.ld, b_kmajor=False,
-                 c=[g.data_ptr() for g in gws], ldc=L.F, c_mode=1, batch0=2,
-                 sA=(hid, 0), sB=(0, 0), beta=1.0, dbias_tab=dbs if fuse else None,
-                 device=dev)
-        _grad_done(*W1s)
-        if not fuse:
-            ops.colsum_grouped(dh.data_ptr(), _dc(cd), 2, ldh, hid, L.rows, hid, dbs,
-                               beta_acc=True, device=dev)
-        _grad_done(*b1s)
 
 
 def mlp_pair(x, mlp_a, mlp_b, out_dtype=None, p=(0.0, 0.0)):
