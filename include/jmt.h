@@ -320,6 +320,67 @@ int jmt_attn_bwd_pds_ok(int N, int H, int Lq, int Lk, int64_t ldp, int64_t sk_l,
 int jmt_attn_dkdv_ok(int N, int H, int Lq, int Lk, int64_t ldp, int64_t sgo_l, int64_t sq_l,
                      int64_t sk_l, int64_t sdk_l, int64_t sdv_l, int64_t sdq_l, int has_dq);
 
+/* Key ranges (key padding masks; added to ABI 7, nothing else changes): padding is contiguous,
+ * so a key padding mask is one run of valid keys [kbeg, kend) per sequence.  kr is a device array
+ * of int32[2 * kr_mod], {kbeg, kend} per entry, 8-B aligned, and sequence n of a launch uses
+ * entry n % kr_mod (kr_mod >= 1 divides N: the 3 B sequences of the grouped encoders and the 6 B
+ * of the cross-attentions share one table of B entries).  Keys outside the range get probability
+ * exactly 0 and lse is the log-sum over the valid keys.  The kernels clamp kbeg to [0, Lk] and
+ * kend to [kbeg, Lk]: a bad table never changes an address; the values of an empty range are
+ * unspecified (NaN).  With every entry {0, Lk} the results are bitwise those of the entry points
+ * without ranges, which launch exactly what they launched before (the range is a compile-time
+ * form of the kernels).
+ *   jmt_attn_fwd_kr / jmt_attn_fwd_sq_kr: as jmt_attn_fwd / jmt_attn_fwd_sq on the whole-row
+ *     kernel (jmt_attn_fwd_rows_ok); anything else returns JMT_ERR_UNSUPPORTED before a launch.
+ *   jmt_attn_bwd_kr / jmt_attn_bwd_sq_kr: as jmt_attn_bwd with dq == NULL / jmt_attn_bwd_sq
+ *     (tile-major P and dS only).  P and dS of keys outside the range are written as zeros in every
+ *     tile the kernel writes, so jmt_attn_dkdv (unchanged) gives zero dK / dV rows for them.
+ *   jmt_attn_short_fwd_kr / jmt_attn_short_bwd_kr: as jmt_attn_short_fwd / jmt_attn_short_bwd.
+ *   jmt_softmax_fwd_kr: as jmt_softmax_fwd; row r belongs to sequence r / rows_per_seq (rows a
+ *     multiple of rows_per_seq, the sequence count a multiple of kr_mod); P is zero outside the
+ *     range, so jmt_softmax_bwd needs none.
+ *   jmt_kpm_ranges: the table of an (N, Lk) byte mask (row stride ld bytes; nonzero = ignore the
+ *     key, torch's key_padding_mask): kr[2 n] = first valid key, kr[2 n + 1] = last valid key + 1
+ *     ({0, 0} without one), and *bad (device int32) += the number of rows that are not exactly
+ *     one non-empty run of valid keys. */
+int jmt_attn_fwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* q, int64_t sq_l,
+                    int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                    int64_t sv_l, int64_t sv_n, void* o, int64_t so_l, int64_t so_n, float scale,
+                    float* lse, const int* kr, int kr_mod, void* stream);
+int jmt_attn_fwd_sq_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* q, int64_t sq_l,
+                       int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                       int64_t sv_l, int64_t sv_n, void* o, int64_t so_l, int64_t so_n,
+                       float scale, float* lse, int spp, const int* qtab, int npair,
+                       const int* kr, int kr_mod, void* stream);
+int jmt_attn_bwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* go, int64_t sgo_l,
+                    int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n, const void* q,
+                    int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                    const void* v, int64_t sv_l, int64_t sv_n, const float* lse, void* p_out,
+                    void* ds_out, int64_t ldp, float scale, const int* kr, int kr_mod,
+                    void* stream);
+int jmt_attn_bwd_sq_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                       int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n,
+                       const void* q, int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                       int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n, const float* lse,
+                       void* p_out, void* ds_out, int64_t ldp, float scale, int spp,
+                       const int* qtab, int npair, const int* kr, int kr_mod, void* stream);
+int jmt_attn_short_fwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                          int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                          const void* v, int64_t sv_l, int64_t sv_n, void* o, int64_t so_l,
+                          int64_t so_n, float scale, float* lse, const int* kr, int kr_mod,
+                          void* stream);
+int jmt_attn_short_bwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                          int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n,
+                          const void* q, int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                          int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n,
+                          const float* lse, void* dq, int64_t sdq_l, int64_t sdq_n, void* dk,
+                          int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n,
+                          float scale, const int* kr, int kr_mod, void* stream);
+int jmt_softmax_fwd_kr(int p_dt, int64_t rows, int n, const float* s, int64_t lds, float scale,
+                       void* p, int64_t ldp, const int* kr, int kr_mod, int64_t rows_per_seq,
+                       void* stream);
+int jmt_kpm_ranges(int N, int Lk, const void* mask, int64_t ld, int* kr, int* bad, void* stream);
+
 /* Fused attention over short sequences, the whole backward in one kernel (Lq, Lk <= 32, 16-bit,
  * dh = 512; the batch-axis self-attention of mm_transformers.py:119-146 at B = 32 and every
  * attention of the T = 16 real-data configuration): same element addressing as jmt_attn_*,

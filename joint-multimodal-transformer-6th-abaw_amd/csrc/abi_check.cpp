@@ -428,6 +428,58 @@ int main() {
                                                             algn, 512, 512, algn, 512, 512, 1, id2,
                                                             2, 1, nullptr));
   }
+  // key ranges: the table arguments are checked on the host, and shapes the range kernels do
+  // not take are refused before anything is launched
+  {
+    alignas(8) const int krt[4] = {0, 300, 5, 290};
+    const int id2[2] = {0, 1};
+#define FWD_KR(N_, Lq_, kr_, mod_)                                                              \
+  jmt_attn_fwd_kr(JMT_BF16, N_, 1, Lq_, 300, 512, algn, 512, 512, algn, 512, 512, algn, 512, 512, \
+                  algn, 512, 512, 0.1f, fnull, kr_, mod_, nullptr)
+#define BWD_KR(N_, kr_, mod_)                                                                   \
+  jmt_attn_bwd_kr(JMT_BF16, N_, 1, 300, 300, 512, algn, 512, 512, algn, 512, 512, algn, 512, 512, \
+                  algn, 512, 512, algn, 512, 512, fnull1, algn, algn, 384, 0.1f, kr_, mod_, nullptr)
+    const float* fnull1 = (const float*)algn;
+    expect_rc("attn_fwd_kr null table", FWD_KR(2, 300, nullptr, 2), JMT_ERR_ARG, "key range table");
+    expect_rc("attn_fwd_kr kr_mod 0", FWD_KR(2, 300, krt, 0), JMT_ERR_ARG, "kr_mod");
+    expect_rc("attn_fwd_kr N % kr_mod", FWD_KR(3, 300, krt, 2), JMT_ERR_ARG, "kr_mod");
+    expect_err("attn_fwd_kr misaligned table", FWD_KR(2, 300, krt + 1, 1));
+    expect_rc("attn_fwd_kr Lq 64 (64-row kernel)", FWD_KR(2, 64, krt, 2), JMT_ERR_UNSUPPORTED,
+              "whole-row kernel only");
+    expect_err("attn_bwd_kr null table", BWD_KR(2, nullptr, 2));
+    expect_rc("attn_bwd_kr N % kr_mod", BWD_KR(3, krt, 2), JMT_ERR_ARG, "kr_mod");
+    expect_err("attn_fwd_sq_kr null table",
+               jmt_attn_fwd_sq_kr(JMT_BF16, 2, 1, 300, 300, 512, algn, 512, 512, algn, 512, 512,
+                                  algn, 512, 512, algn, 512, 512, 0.1f, fnull, 1, id2, 2, nullptr,
+                                  2, nullptr));
+    expect_err("attn_bwd_sq_kr kr_mod 0",
+               jmt_attn_bwd_sq_kr(JMT_BF16, 2, 1, 300, 300, 512, algn, 512, 512, algn, 512, 512,
+                                  algn, 512, 512, algn, 512, 512, algn, 512, 512, fnull1, algn,
+                                  algn, 384, 0.1f, 1, id2, 2, krt, 0, nullptr));
+    expect_err("attn_short_fwd_kr null table",
+               jmt_attn_short_fwd_kr(JMT_BF16, 2, 1, 16, 16, 512, algn, 512, 512, algn, 512, 512,
+                                     algn, 512, 512, algn, 512, 512, 0.1f, fnull, nullptr, 2,
+                                     nullptr));
+    expect_err("attn_short_fwd_kr Lk 33",
+               jmt_attn_short_fwd_kr(JMT_BF16, 2, 1, 16, 33, 512, algn, 512, 512, algn, 512, 512,
+                                     algn, 512, 512, algn, 512, 512, 0.1f, fnull, krt, 2, nullptr));
+    expect_err("attn_short_bwd_kr N % kr_mod",
+               jmt_attn_short_bwd_kr(JMT_BF16, 3, 1, 16, 16, 512, algn, 512, 512, algn, 512, 512,
+                                     algn, 512, 512, algn, 512, 512, algn, 512, 512, fnull1, algn,
+                                     512, 512, algn, 512, 512, algn, 512, 512, 0.1f, krt, 2,
+                                     nullptr));
+    expect_err("softmax_fwd_kr null table",
+               jmt_softmax_fwd_kr(JMT_BF16, 8, 300, fnull1, 304, 1.f, algn, 304, nullptr, 2, 4,
+                                  nullptr));
+    expect_err("softmax_fwd_kr sequences % kr_mod",
+               jmt_softmax_fwd_kr(JMT_BF16, 12, 300, fnull1, 304, 1.f, algn, 304, krt, 2, 4,
+                                  nullptr));
+    expect_err("kpm_ranges null", jmt_kpm_ranges(2, 300, nullptr, 300, nullptr, nullptr, nullptr));
+    expect_err("kpm_ranges ld < Lk", jmt_kpm_ranges(2, 300, algn, 200, (int*)algn, (int*)algn,
+                                                    nullptr));
+#undef FWD_KR
+#undef BWD_KR
+  }
   expect_err("small_attn_fwd null", jmt_small_attn_fwd(JMT_BF16, 4, 1, 6, 6, 512, nullptr, 512,
                                                        512, nullptr, 512, 512, nullptr, 512, 512,
                                                        nullptr, 512, 512, 0.1f, fnull, nullptr));

@@ -622,8 +622,12 @@ constexpr int AP_LDS = 4 * AP_KT * AT_ROWB;
 // (s_memtime of block gridDim / 2, waves 0 and 4, into p.dq as a uint64 buffer of
 // 2 x 256 x 64: phases 8 t + {0 tile start, 1 DMA issued, 2 MFMAs issued, 3 softmax + stores
 // issued, 4 end wait, 5 barrier} of the block's first 31 tiles, 255 / 254 item start / end)
-template <typename T, int DBG = 0, bool SQ = false>
-__global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(AttnBwdArgs p) {
+// KR: key ranges (attn_common.h KeyRange).  P and dS of keys outside the item's range are written
+// as exact zeros in every tile (jmt_attn_dkdv reads whole tiles), so dK / dV of masked keys come
+// out as zeros from the zero columns; no tile is skipped and the counted waits are untouched.
+// The range of the next item is read where its n2 is formed and carried in two SGPRs.
+template <typename T, int DBG = 0, bool SQ = false, bool KR = false>
+__global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(KrArgs<AttnBwdArgs, KR> p) {
   int tcount = 0;
   auto st = [&](int phase) {
     if constexpr ((DBG & 64) != 0) {
@@ -692,6 +696,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(AttnBwdArgs p) {
     }
   };
   stage_tile(0, kb, vb, 0);
+  int kbeg, kend;                                 // valid keys of this item (KR; else [0, Lk))
+  key_range<KR>(p, n, p.Lk, kbeg, kend);
 
   int kb4[4];                                     // ds_read_b128 lane bases (whole row)
 #pragma unroll
@@ -707,6 +713,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(AttnBwdArgs p) {
     const int nh2 = nxt / nqt, n2 = nh2 / p.H, hd2 = nh2 % p.H, q02 = (nxt % nqt) * AP_QT;
     const T* kb2 = (const T*)p.k + (int64_t)n2 * p.sk_n + hd2 * AT_DH;
     const T* vb2 = (const T*)p.v + (int64_t)n2 * p.sv_n + hd2 * AT_DH;
+    int kbeg2, kend2;
+    key_range<KR>(p, more ? n2 : n, p.Lk, kbeg2, kend2);
 
     float delta;                                  // rowsum(dO o O) of row qr
     {
@@ -801,7 +809,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(AttnBwdArgs p) {
           T pv4[4], ds4[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const bool in = kbase + 16 * kt + r < p.Lk;
+            const int key = kbase + 16 * kt + r;
+            const bool in = KR ? (key >= kbeg && key < kend) : key < p.Lk;
             const float pv = in ? __builtin_amdgcn_exp2f(s[kt][r] * p.scale_log2 - lse2) : 0.f;
             pv4[r] = from_f<T>(pv);
             ds4[r] = from_f<T>(p.scale * pv * (d[kt][r] - delta));
@@ -854,6 +863,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_pds_kernel(AttnBwdArgs p) {
     // waited for the tile's DMA right after issuing it)
     if constexpr ((DBG & 1) == 0) load_o(n2, hd2, q02);
     item = nxt; nh = nh2; n = n2; hd = hd2; q0 = q02; kb = kb2; vb = vb2;
+    kbeg = kbeg2; kend = kend2;
   }
 }
 
@@ -888,8 +898,12 @@ constexpr int AR_VB = 4;             // V fragments per P V read batch
 // DBG (ablations, timing only, wrong results; JMT_ATTN_FWD_ROWS_DBG in the diagnostic build):
 // 2 no score reads / MFMAs, 4 no softmax, 8 no K / V DMA after an item's tile 0, 16 no P V reads /
 // MFMAs, 32 no O / lse stores.
-template <typename T, int DBG = 0, bool SQ = false>
-__global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
+// KR: key ranges (attn_common.h KeyRange): keys outside the item's range score -inf and get
+// probability exactly 0 (selected, not exponentiated: a whole tile left of the range leaves the
+// running max at -inf, and exp2(-inf - -inf) is NaN); lse is over the valid keys.  Every tile is
+// still staged and multiplied (masking only; skipping tiles outside the range is not built).
+template <typename T, int DBG = 0, bool SQ = false, bool KR = false>
+__global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(KrArgs<AttnFwdArgs, KR> p) {
   typedef typename Frag16<T>::t F;
   typedef typename Frag16<T>::h Hf;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -937,6 +951,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
     }
   };
   stage_tile(0, kb, vb, 0);
+  int kbeg, kend;                                 // valid keys of this item (KR; else [0, Lk))
+  key_range<KR>(p, n, p.Lk, kbeg, kend);
   // Lane bases of the fragment reads: row_base(m) = row_base(0) ^ (m << 6) and tr_base(c) =
   // tr_base(0) ^ (c << 5) (the swizzle XOR and m / c sit in the same chunk bits), formed by one
   // VALU XOR in front of the reads that use them instead of living in 12 registers over the
@@ -962,6 +978,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
     const int nh2 = nxt / nqt, n2 = nh2 / p.H, hd2 = nh2 % p.H, q02 = (nxt % nqt) * AR_QT;
     const T* kb2 = (const T*)p.k + (int64_t)n2 * p.sk_n + hd2 * AT_DH;
     const T* vb2 = (const T*)p.v + (int64_t)n2 * p.sv_n + hd2 * AT_DH;
+    int kbeg2, kend2;
+    key_range<KR>(p, more ? n2 : n, p.Lk, kbeg2, kend2);
 
     f32x4 o[32];
 #pragma unroll
@@ -1038,12 +1056,15 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
           const f32x4 full = sl[kt] + sh[kt];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float x = (kbase + 16 * kt + r < p.Lk) ? full[r] * p.scale_log2 : -INFINITY;
+            const int key = kbase + 16 * kt + r;
+            const bool in = KR ? (key >= kbeg && key < kend) : key < p.Lk;
+            const float x = in ? full[r] * p.scale_log2 : -INFINITY;
             sl[kt][r] = x;
             mx = fmaxf(mx, x);
           }
         }
         mx = pl_pair_max(mx);
+        if constexpr (!KR) {
         if (__any(mx > m_run + 8.f)) {
           const float m_new = fmaxf(m_run, mx);
           const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
@@ -1052,12 +1073,35 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
 #pragma unroll
           for (int t = 0; t < 32; ++t) o[t] *= alpha;
         }
+        } else {
+        // The vote is the wave's, for its 16 query rows together, so a row's rounding depends on
+        // its neighbours' scores.  With ranges, a query row whose own index is a masked key (a
+        // padded frame where queries and keys share the axis) takes no part in the vote of the
+        // other rows: those rescale only when one of them asks (else alpha = 1, a bitwise no-op),
+        // the masked-index rows whenever the branch is entered.  Any such schedule is a correct
+        // lazy rescale (a row that needs it always gets it); this one keeps the values at valid
+        // frames independent of what the padded frames hold, and with nothing masked it is the
+        // vote above (bitwise the kernel without ranges).
+        const bool need = mx > m_run + 8.f;
+        if (__any(need)) {
+          const int qc = min(qr, p.Lq - 1);         // rows past Lq repeat row Lq - 1
+          const bool qin = !(qc < kbeg || (qc >= kend && qc < p.Lk));
+          const bool apply = !qin || __any(need && qin);
+          const float m_new = apply ? fmaxf(m_run, mx) : m_run;
+          const float alpha = apply ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.f;
+          m_run = m_new;
+          l_run *= alpha;
+#pragma unroll
+          for (int t = 0; t < 32; ++t) o[t] *= alpha;
+        }
+        }
         float ls = 0.f;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float pv = __builtin_amdgcn_exp2f(sl[kt][r] - m_run);
+            float pv = __builtin_amdgcn_exp2f(sl[kt][r] - m_run);
+            if constexpr (KR) pv = sl[kt][r] == -INFINITY ? 0.f : pv;
             ls += pv;
             pf[kt * 4 + r] = from_f<T>(pv);
           }
@@ -1121,6 +1165,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_rows_kernel(AttnFwdArgs p) {
     }
     if (!more) break;
     item = nxt; nh = nh2; n = n2; hd = hd2; q0 = q02; kb = kb2; vb = vb2;
+    kbeg = kbeg2; kend = kend2;
   }
 }
 
@@ -1239,11 +1284,12 @@ extern "C" int jmt_attn_bwd_pds_ok(int N, int H, int Lq, int Lk, int64_t ldp, in
 }
 
 // jmt_attn_fwd (qs == NULL) and jmt_attn_fwd_sq (qs: the packed query table; the whole-row
-// kernel only)
+// kernel only); kr: the key range table of the *_kr forms (the whole-row kernel only)
 static int attn_fwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
                          int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
                          const void* v, int64_t sv_l, int64_t sv_n, void* o, int64_t so_l,
-                         int64_t so_n, float scale, float* lse, const QShare* qs, void* stream) {
+                         int64_t so_n, float scale, float* lse, const QShare* qs,
+                         const KeyRange* kr, void* stream) {
   if (N == 0 || Lq == 0) return JMT_OK;
   if (!jmt_attn_supported(dt, dh))
     return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_fwd: dtype %d / head dim %d not supported",
@@ -1255,9 +1301,14 @@ static int attn_fwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const voi
     return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_fwd_sq: the whole-row kernel only (Lq > %d, "
                                           "Lk K / V rows below 2 GiB, JMT_ATTN_FWD_ROWS on)",
                      AT_QT);
+  if (kr && !rows)
+    return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_fwd_kr: the whole-row kernel only (Lq > %d, "
+                                          "Lk K / V rows below 2 GiB, JMT_ATTN_FWD_ROWS on)",
+                     AT_QT);
   const int qt = rows ? AR_QT : AT_QT;
   int rc = check_common("jmt_attn_fwd", N, H, Lq, Lk, qt, ptrs, 4, strides, 8);
   if (rc != JMT_OK) return rc;
+  if (kr && (rc = key_range_check("jmt_attn_fwd_kr", N, kr->tab, kr->mod)) != JMT_OK) return rc;
   AttnFwdArgs a = {};
   if (qs) a.qs = *qs;
   a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
@@ -1294,6 +1345,13 @@ static int attn_fwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const voi
   by_elem(dt, [&](auto e) {
     using T = typename decltype(e)::type;
     if (!rows) attn_launch<attn_fwd_kernel<T, false, ATTN_FWD_OPT>, AF_LDS>(grid, st, a);
+    else if (kr) {
+      WithKeyRange<AttnFwdArgs> ak;
+      static_cast<AttnFwdArgs&>(ak) = a;
+      ak.kr = *kr;
+      if (qs) attn_launch<attn_fwd_rows_kernel<T, 0, true, true>, AR_LDS>(grid, st, ak);
+      else attn_launch<attn_fwd_rows_kernel<T, 0, false, true>, AR_LDS>(grid, st, ak);
+    }
     else if (qs) attn_launch<attn_fwd_rows_kernel<T, 0, true>, AR_LDS>(grid, st, a);
     else attn_launch<attn_fwd_rows_kernel<T>, AR_LDS>(grid, st, a);
   });
@@ -1306,7 +1364,17 @@ extern "C" int jmt_attn_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
                             const void* v, int64_t sv_l, int64_t sv_n, void* o, int64_t so_l,
                             int64_t so_n, float scale, float* lse, void* stream) {
   return attn_fwd_impl(dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o, so_l,
-                       so_n, scale, lse, nullptr, stream);
+                       so_n, scale, lse, nullptr, nullptr, stream);
+}
+
+extern "C" int jmt_attn_fwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                               int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                               int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n, void* o,
+                               int64_t so_l, int64_t so_n, float scale, float* lse,
+                               const int* kr, int kr_mod, void* stream) {
+  const KeyRange r = {kr, kr_mod};
+  return attn_fwd_impl(dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o, so_l,
+                       so_n, scale, lse, nullptr, &r, stream);
 }
 
 extern "C" int jmt_attn_fwd_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
@@ -1322,17 +1390,36 @@ extern "C" int jmt_attn_fwd_sq(int dt, int N, int H, int Lq, int Lk, int dh, con
   int rc = qshare_pack("jmt_attn_fwd_sq", N, spp, qtab, npair, &qs);
   if (rc != JMT_OK) return rc;
   return attn_fwd_impl(dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o, so_l,
-                       so_n, scale, lse, &qs, stream);
+                       so_n, scale, lse, &qs, nullptr, stream);
 }
 
-// jmt_attn_bwd (qs == NULL) and jmt_attn_bwd_sq (qs: the packed query table; dq == NULL only)
+extern "C" int jmt_attn_fwd_sq_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                                  int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                                  int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n, void* o,
+                                  int64_t so_l, int64_t so_n, float scale, float* lse, int spp,
+                                  const int* qtab, int npair, const int* kr, int kr_mod,
+                                  void* stream) {
+  if (N == 0 || Lq == 0) return JMT_OK;
+  if (!jmt_attn_supported(dt, dh))
+    return set_error(JMT_ERR_UNSUPPORTED,
+                     "jmt_attn_fwd_sq_kr: dtype %d / head dim %d not supported", dt, dh);
+  QShare qs = {};
+  int rc = qshare_pack("jmt_attn_fwd_sq_kr", N, spp, qtab, npair, &qs);
+  if (rc != JMT_OK) return rc;
+  const KeyRange r = {kr, kr_mod};
+  return attn_fwd_impl(dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o, so_l,
+                       so_n, scale, lse, &qs, &r, stream);
+}
+
+// jmt_attn_bwd (qs == NULL) and jmt_attn_bwd_sq (qs: the packed query table; dq == NULL only);
+// kr: the key range table of the *_kr forms (dq == NULL only)
 static int attn_bwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
                          int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n,
                          const void* q, int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
                          int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n,
                          const float* lse, void* p_out, void* ds_out, int64_t ldp, void* dq,
                          int64_t sdq_l, int64_t sdq_n, float scale, const QShare* qs,
-                         void* stream) {
+                         const KeyRange* kr, void* stream) {
   if (N == 0 || Lq == 0) return JMT_OK;
   if (!jmt_attn_supported(dt, dh))
     return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_bwd: dtype %d / head dim %d not supported",
@@ -1341,6 +1428,8 @@ static int attn_bwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const voi
   const int64_t strides[] = {sgo_l, sgo_n, so_l, so_n, sq_l, sq_n, sk_l, sk_n, sv_l, sv_n, ldp,
                              sdq_l, sdq_n};
   const bool pds = dq == nullptr;                 // P / dS only: dQ left to jmt_attn_dkdv
+  if (kr && !pds)
+    return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_bwd_kr: the P / dS kernel only (dq = NULL)");
   const int qt = pds ? AP_QT : AT_QT;
   int rc = check_common("jmt_attn_bwd", N, H, Lq, Lk, qt, ptrs, pds ? 7 : 8, strides,
                         pds ? 11 : 13);
@@ -1350,6 +1439,7 @@ static int attn_bwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const voi
     const char* why = pds_range(N, H, Lq, Lk, ldp, sk_l, sv_l);
     JMT_CHECK_ARG(!why, "jmt_attn_bwd (dq = NULL): %s", why);
   }
+  if (kr && (rc = key_range_check("jmt_attn_bwd_kr", N, kr->tab, kr->mod)) != JMT_OK) return rc;
   AttnBwdArgs a = {};
   if (qs) a.qs = *qs;
   a.go = go; a.o = o; a.q = q; a.k = k; a.v = v; a.lse = lse;
@@ -1385,6 +1475,13 @@ static int attn_bwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const voi
   by_elem(dt, [&](auto e) {
     using T = typename decltype(e)::type;
     if (!pds) attn_launch<attn_bwd_kernel<T, ATTN_BWD_OPT>, AB_LDS>(grid, st, a);
+    else if (kr) {
+      WithKeyRange<AttnBwdArgs> ak;
+      static_cast<AttnBwdArgs&>(ak) = a;
+      ak.kr = *kr;
+      if (qs) attn_launch<attn_bwd_pds_kernel<T, 0, true, true>, AP_LDS>(grid, st, ak);
+      else attn_launch<attn_bwd_pds_kernel<T, 0, false, true>, AP_LDS>(grid, st, ak);
+    }
     else if (qs) attn_launch<attn_bwd_pds_kernel<T, 0, true>, AP_LDS>(grid, st, a);
     else attn_launch<attn_bwd_pds_kernel<T>, AP_LDS>(grid, st, a);
   });
@@ -1401,7 +1498,21 @@ extern "C" int jmt_attn_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const 
                             float scale, void* stream) {
   return attn_bwd_impl(dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
                        sk_l, sk_n, v, sv_l, sv_n, lse, p_out, ds_out, ldp, dq, sdq_l, sdq_n, scale,
-                       nullptr, stream);
+                       nullptr, nullptr, stream);
+}
+
+// the dq == NULL form only (P / dS for jmt_attn_dkdv)
+extern "C" int jmt_attn_bwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                               int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
+                               int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
+                               const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                               int64_t sv_l, int64_t sv_n, const float* lse, void* p_out,
+                               void* ds_out, int64_t ldp, float scale, const int* kr, int kr_mod,
+                               void* stream) {
+  const KeyRange r = {kr, kr_mod};
+  return attn_bwd_impl(dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
+                       sk_l, sk_n, v, sv_l, sv_n, lse, p_out, ds_out, ldp, nullptr, 0, 0, scale,
+                       nullptr, &r, stream);
 }
 
 extern "C" int jmt_attn_bwd_sq(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
@@ -1420,5 +1531,26 @@ extern "C" int jmt_attn_bwd_sq(int dt, int N, int H, int Lq, int Lk, int dh, con
   if (rc != JMT_OK) return rc;
   return attn_bwd_impl(dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
                        sk_l, sk_n, v, sv_l, sv_n, lse, p_out, ds_out, ldp, nullptr, 0, 0, scale,
-                       &qs, stream);
+                       &qs, nullptr, stream);
+}
+
+extern "C" int jmt_attn_bwd_sq_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                                  int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
+                                  int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
+                                  const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                                  int64_t sv_l, int64_t sv_n, const float* lse, void* p_out,
+                                  void* ds_out, int64_t ldp, float scale, int spp,
+                                  const int* qtab, int npair, const int* kr, int kr_mod,
+                                  void* stream) {
+  if (N == 0 || Lq == 0) return JMT_OK;
+  if (!jmt_attn_supported(dt, dh))
+    return set_error(JMT_ERR_UNSUPPORTED,
+                     "jmt_attn_bwd_sq_kr: dtype %d / head dim %d not supported", dt, dh);
+  QShare qs = {};
+  int rc = qshare_pack("jmt_attn_bwd_sq_kr", N, spp, qtab, npair, &qs);
+  if (rc != JMT_OK) return rc;
+  const KeyRange r = {kr, kr_mod};
+  return attn_bwd_impl(dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
+                       sk_l, sk_n, v, sv_l, sv_n, lse, p_out, ds_out, ldp, nullptr, 0, 0, scale,
+                       &qs, &r, stream);
 }

@@ -2,6 +2,8 @@
 // Lq, Lk <= 32), head dim 512: the swizzled K / V / Q / dO row images in LDS and their fragment
 // reads, LDS-DMA row staging, lane-group reductions, the register-direct output store.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace jmt {
@@ -43,6 +45,62 @@ static inline int qshare_pack(const char* name, int N, int spp, const int* tab, 
   }
   out->spp = spp;
   out->tab = bits;
+  return JMT_OK;
+}
+
+// Key ranges (the *_kr entry points): key padding as one run of valid keys [kbeg, kend) per
+// sequence.  tab is a device array of int32 {kbeg, kend} pairs and sequence n uses entry n % mod
+// (the 3 B sequences of the grouped encoders and the 6 B of the cross-attentions share one table
+// of B entries).  A block works on one (n, h) at a time, so the range is wave-uniform: two SGPRs
+// read by one scalar load per item, no per-lane mask.  Keys outside the range get probability 0.
+struct KeyRange {
+  const int* tab;
+  int mod;
+};
+// The kernels are compiled twice: KR = false (the entry points without ranges: the parent's code,
+// the key test is `key < Lk`) and KR = true.  The range is clamped to [0, Lk] (kbeg <= kend), so
+// a bad table changes values, never addresses; an empty range gives unspecified values (NaN).
+// The table travels behind the kernel's arguments (KrArgs<A, true>), so the argument block of
+// the KR = false instantiations is the parent's, byte for byte.
+template <typename A>
+struct WithKeyRange : A {
+  KeyRange kr;
+};
+template <typename A, bool KR>
+using KrArgs = std::conditional_t<KR, WithKeyRange<A>, A>;
+
+template <bool KR, typename A>
+__device__ __forceinline__ void key_range(const A& p, int n, int Lk, int& kbeg, int& kend) {
+  if constexpr (!KR) {
+    kbeg = 0;
+    kend = Lk;
+  } else {
+    const KeyRange& r = p.kr;
+    const int e = __builtin_amdgcn_readfirstlane(n % r.mod);
+    const int* a = r.tab + 2 * (int64_t)e;
+    int b0, b1;
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__OPTIMIZE__)
+    // one scalar load, waited for on the spot (once per item; invisible to hipcc's own counts,
+    // and no vector load that the kernels' counted vmcnt waits would have to include)
+    typedef int i32x2 __attribute__((ext_vector_type(2)));
+    i32x2 v;
+    asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(a) : "memory");
+    b0 = v[0];
+    b1 = v[1];
+#else
+    b0 = a[0];                                    // unoptimised device code (the host-ASan
+    b1 = a[1];                                    // build, never launched) keeps `a` in VGPRs
+#endif
+    kbeg = min(max(b0, 0), Lk);
+    kend = min(max(b1, kbeg), Lk);
+  }
+}
+// Host side: the checks every *_kr entry point makes on its table arguments
+static inline int key_range_check(const char* name, int N, const int* tab, int mod) {
+  JMT_CHECK_ARG(tab != nullptr && ((uintptr_t)tab & 7) == 0, "%s: key range table null or not "
+                "8-B aligned", name);
+  JMT_CHECK_ARG(mod >= 1 && N % mod == 0, "%s: kr_mod %d must be >= 1 and divide N %d", name, mod,
+                N);
   return JMT_OK;
 }
 

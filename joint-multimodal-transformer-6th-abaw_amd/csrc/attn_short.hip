@@ -52,8 +52,10 @@ struct AttnShortArgs {
   float scale, scale_log2;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256, 2) void attn_short_fwd_kernel(AttnShortArgs p) {
+// KR (both kernels): key ranges (attn_common.h KeyRange); the backward needs the range in its
+// recompute of P from lse, where a masked key would otherwise get exp(s - lse) != 0.
+template <typename T, bool KR = false>
+__global__ __launch_bounds__(256, 2) void attn_short_fwd_kernel(KrArgs<AttnShortArgs, KR> p) {
   typedef typename Frag16<T>::t F;
   typedef typename Frag16<T>::h Hf;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -65,6 +67,8 @@ __global__ __launch_bounds__(256, 2) void attn_short_fwd_kernel(AttnShortArgs p)
   const int g = lane >> 4, li = lane & 15, h = w >> 1;
   const int nh = blockIdx.x, n = nh / p.H, hd = nh % p.H;
   const int qr = 16 * (w & 1) + li;
+  int kbeg, kend;
+  key_range<KR>(p, n, p.Lk, kbeg, kend);
   stage_rows<T, AS_L, 4>(kimg, (const T*)p.k + (int64_t)n * p.sk_n + hd * AT_DH, p.sk_l, 0, p.Lk);
   stage_rows<T, AS_L, 4>(vimg, (const T*)p.v + (int64_t)n * p.sv_n + hd * AT_DH, p.sv_l, 0, p.Lk);
   F qf[8];
@@ -101,7 +105,9 @@ __global__ __launch_bounds__(256, 2) void attn_short_fwd_kernel(AttnShortArgs p)
     const f32x4 full = h == 0 ? s[kt] + ps : ps + s[kt];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      x[kt][r] = (16 * kt + 4 * g + r < p.Lk) ? full[r] * p.scale_log2 : -INFINITY;
+      const int key = 16 * kt + 4 * g + r;
+      const bool in = KR ? (key >= kbeg && key < kend) : key < p.Lk;
+      x[kt][r] = in ? full[r] * p.scale_log2 : -INFINITY;
       mx = fmaxf(mx, x[kt][r]);
     }
   }
@@ -135,8 +141,8 @@ __global__ __launch_bounds__(256, 2) void attn_short_fwd_kernel(AttnShortArgs p)
                       qr < p.Lq);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256, 1) void attn_short_bwd_kernel(AttnShortArgs p) {
+template <typename T, bool KR = false>
+__global__ __launch_bounds__(256, 1) void attn_short_bwd_kernel(KrArgs<AttnShortArgs, KR> p) {
   typedef typename Frag16<T>::t F;
   typedef typename Frag16<T>::h Hf;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -154,6 +160,8 @@ __global__ __launch_bounds__(256, 1) void attn_short_bwd_kernel(AttnShortArgs p)
   const int nh = blockIdx.x, n = nh / p.H, hd = nh % p.H;
   const int qr = rb + li, qc = min(qr, p.Lq - 1);
   const int64_t hoff = (int64_t)hd * AT_DH;
+  int kbeg, kend;
+  key_range<KR>(p, n, p.Lk, kbeg, kend);
   stage_rows<T, AS_L, 4>(qimg, (const T*)p.q + (int64_t)n * p.sq_n + hoff, p.sq_l, 0, p.Lq);
   stage_rows<T, AS_L, 4>(kimg, (const T*)p.k + (int64_t)n * p.sk_n + hoff, p.sk_l, 0, p.Lk);
   stage_rows<T, AS_L, 4>(vimg, (const T*)p.v + (int64_t)n * p.sv_n + hoff, p.sv_l, 0, p.Lk);
@@ -225,7 +233,7 @@ __global__ __launch_bounds__(256, 1) void attn_short_bwd_kernel(AttnShortArgs p)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int key = 16 * kt + 4 * g + r;
-      const bool in = key < p.Lk && qr < p.Lq;
+      const bool in = (KR ? (key >= kbeg && key < kend) : key < p.Lk) && qr < p.Lq;
       const float pv = in ? __builtin_amdgcn_exp2f(sf[r] * p.scale_log2 - lse2) : 0.f;
       const T ds = from_f<T>(p.scale * pv * (dfull[r] - delta));
       dsf[kt * 4 + r] = ds;
@@ -315,11 +323,12 @@ extern "C" int jmt_attn_short_supported(int dt, int dh, int Lq, int Lk) {
          Lk <= AS_L;
 }
 
-extern "C" int jmt_attn_short_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
-                                  int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
-                                  int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n, void* o,
-                                  int64_t so_l, int64_t so_n, float scale, float* lse,
-                                  void* stream) {
+// jmt_attn_short_fwd (kr == NULL) and jmt_attn_short_fwd_kr
+static int short_fwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                          int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                          const void* v, int64_t sv_l, int64_t sv_n, void* o, int64_t so_l,
+                          int64_t so_n, float scale, float* lse, const KeyRange* kr,
+                          void* stream) {
   if (N == 0 || Lq == 0) return JMT_OK;
   if (!jmt_attn_short_supported(dt, dh, Lq, Lk))
     return set_error(JMT_ERR_UNSUPPORTED,
@@ -329,6 +338,8 @@ extern "C" int jmt_attn_short_fwd(int dt, int N, int H, int Lq, int Lk, int dh, 
   const int64_t strides[] = {sq_l, sq_n, sk_l, sk_n, sv_l, sv_n, so_l, so_n};
   int rc = as_check("jmt_attn_short_fwd", N, H, Lq, Lk, ptrs, 4, strides, 8);
   if (rc != JMT_OK) return rc;
+  if (kr && (rc = key_range_check("jmt_attn_short_fwd_kr", N, kr->tab, kr->mod)) != JMT_OK)
+    return rc;
   AttnShortArgs a = {};
   a.q = q; a.k = k; a.v = v; a.out = o; a.lse = lse;
   a.sq_l = sq_l; a.sq_n = sq_n; a.sk_l = sk_l; a.sk_n = sk_n; a.sv_l = sv_l; a.sv_n = sv_n;
@@ -339,20 +350,46 @@ extern "C" int jmt_attn_short_fwd(int dt, int N, int H, int Lq, int Lk, int dh, 
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(N * H));
   by_elem(dt, [&](auto e) {
-    attn_launch<attn_short_fwd_kernel<typename decltype(e)::type>, ASF_LDS, 256>(grid, st, a);
+    using T = typename decltype(e)::type;
+    if (kr) {
+      WithKeyRange<AttnShortArgs> ak;
+      static_cast<AttnShortArgs&>(ak) = a;
+      ak.kr = *kr;
+      attn_launch<attn_short_fwd_kernel<T, true>, ASF_LDS, 256>(grid, st, ak);
+    }
+    else attn_launch<attn_short_fwd_kernel<T>, ASF_LDS, 256>(grid, st, a);
   });
   JMT_LAUNCH_CHECK("jmt_attn_short_fwd");
   return JMT_OK;
 }
 
-extern "C" int jmt_attn_short_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
-                                  int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
-                                  int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
-                                  const void* k, int64_t sk_l, int64_t sk_n, const void* v,
-                                  int64_t sv_l, int64_t sv_n, const float* lse, void* dq,
-                                  int64_t sdq_l, int64_t sdq_n, void* dk, int64_t sdk_l,
-                                  int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n,
-                                  float scale, void* stream) {
+extern "C" int jmt_attn_short_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                                  int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                                  int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n, void* o,
+                                  int64_t so_l, int64_t so_n, float scale, float* lse,
+                                  void* stream) {
+  return short_fwd_impl(dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o, so_l,
+                        so_n, scale, lse, nullptr, stream);
+}
+
+extern "C" int jmt_attn_short_fwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                                     int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                                     int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n,
+                                     void* o, int64_t so_l, int64_t so_n, float scale, float* lse,
+                                     const int* kr, int kr_mod, void* stream) {
+  const KeyRange r = {kr, kr_mod};
+  return short_fwd_impl(dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o, so_l,
+                        so_n, scale, lse, &r, stream);
+}
+
+// jmt_attn_short_bwd (kr == NULL) and jmt_attn_short_bwd_kr
+static int short_bwd_impl(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                          int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n,
+                          const void* q, int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                          int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n,
+                          const float* lse, void* dq, int64_t sdq_l, int64_t sdq_n, void* dk,
+                          int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n,
+                          float scale, const KeyRange* kr, void* stream) {
   if (N == 0 || Lq == 0) return JMT_OK;
   if (!jmt_attn_short_supported(dt, dh, Lq, Lk))
     return set_error(JMT_ERR_UNSUPPORTED,
@@ -364,6 +401,8 @@ extern "C" int jmt_attn_short_bwd(int dt, int N, int H, int Lq, int Lk, int dh, 
   int rc = as_check("jmt_attn_short_bwd", N, H, Lq, Lk, ptrs, 8, strides, 16);
   if (rc != JMT_OK) return rc;
   JMT_CHECK_ARG(lse != nullptr, "jmt_attn_short_bwd: lse missing");
+  if (kr && (rc = key_range_check("jmt_attn_short_bwd_kr", N, kr->tab, kr->mod)) != JMT_OK)
+    return rc;
   AttnShortArgs a = {};
   a.q = q; a.k = k; a.v = v; a.o = o; a.go = go; a.lse = (float*)lse;
   a.dq = dq; a.dk = dk; a.dv = dv;
@@ -377,8 +416,42 @@ extern "C" int jmt_attn_short_bwd(int dt, int N, int H, int Lq, int Lk, int dh, 
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(N * H));
   by_elem(dt, [&](auto e) {
-    attn_launch<attn_short_bwd_kernel<typename decltype(e)::type>, ASB_LDS, 256>(grid, st, a);
+    using T = typename decltype(e)::type;
+    if (kr) {
+      WithKeyRange<AttnShortArgs> ak;
+      static_cast<AttnShortArgs&>(ak) = a;
+      ak.kr = *kr;
+      attn_launch<attn_short_bwd_kernel<T, true>, ASB_LDS, 256>(grid, st, ak);
+    }
+    else attn_launch<attn_short_bwd_kernel<T>, ASB_LDS, 256>(grid, st, a);
   });
   JMT_LAUNCH_CHECK("jmt_attn_short_bwd");
   return JMT_OK;
+}
+
+extern "C" int jmt_attn_short_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                                  int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
+                                  int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
+                                  const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                                  int64_t sv_l, int64_t sv_n, const float* lse, void* dq,
+                                  int64_t sdq_l, int64_t sdq_n, void* dk, int64_t sdk_l,
+                                  int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n,
+                                  float scale, void* stream) {
+  return short_bwd_impl(dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
+                        sk_l, sk_n, v, sv_l, sv_n, lse, dq, sdq_l, sdq_n, dk, sdk_l, sdk_n, dv,
+                        sdv_l, sdv_n, scale, nullptr, stream);
+}
+
+extern "C" int jmt_attn_short_bwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                                     int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
+                                     int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
+                                     const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                                     int64_t sv_l, int64_t sv_n, const float* lse, void* dq,
+                                     int64_t sdq_l, int64_t sdq_n, void* dk, int64_t sdk_l,
+                                     int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n,
+                                     float scale, const int* kr, int kr_mod, void* stream) {
+  const KeyRange r = {kr, kr_mod};
+  return short_bwd_impl(dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
+                        sk_l, sk_n, v, sv_l, sv_n, lse, dq, sdq_l, sdq_n, dk, sdk_l, sdk_n, dv,
+                        sdv_l, sdv_n, scale, &r, stream);
 }

@@ -640,6 +640,65 @@ __global__ __launch_bounds__(RB) void softmax_fwd_kernel(int64_t rows, int n, co
     pr[c] = from_f<TP>(c < n ? __expf(sr[c] * scale - m) * iz : 0.f);
 }
 
+// The key-range form (jmt_softmax_fwd_kr; a kernel of its own, softmax_fwd_kernel is untouched):
+// row r belongs to sequence r / rows_per_seq and uses entry (sequence % kr_mod) of the int32
+// {kbeg, kend} table; the softmax runs over columns [kbeg, kend) (clamped to [0, n]) and P is
+// written as zero everywhere else, so softmax_bwd_kernel needs no range (P = 0 gives dS = 0).
+template <typename TP>
+__global__ __launch_bounds__(RB) void softmax_fwd_kr_kernel(int64_t rows, int n, const float* s,
+                                                            int64_t lds, float scale, TP* p,
+                                                            int64_t ldp, const int* kr, int kr_mod,
+                                                            int64_t rows_per_seq) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= rows) return;
+  const int* e = kr + 2 * ((r / rows_per_seq) % kr_mod);
+  const int c0 = min(max(e[0], 0), n), c1 = min(max(e[1], c0), n);
+  const float* sr = s + r * lds;
+  float m = -INFINITY;
+  for (int c = c0 + lane; c < c1; c += 64) m = fmaxf(m, sr[c] * scale);
+  m = wave_max(m);
+  float z = 0.f;
+  for (int c = c0 + lane; c < c1; c += 64) z += __expf(sr[c] * scale - m);
+  z = wave_sum(z);
+  const float iz = 1.f / z;
+  TP* pr = p + r * ldp;
+  for (int c = lane; c < ldp; c += 64)
+    pr[c] = from_f<TP>(c >= c0 && c < c1 ? __expf(sr[c] * scale - m) * iz : 0.f);
+}
+
+// Key padding mask -> key range table (jmt_kpm_ranges).  One wave per mask row (N rows of Lk
+// bytes, nonzero = ignore): the row's valid keys are counted and their first and last positions
+// found; the row is one non-empty run exactly when last - first + 1 equals the count.  Writes
+// {first, last + 1} ({0, 0} for a row without a valid key) and adds the rows that are not one
+// non-empty run to *bad.
+__global__ __launch_bounds__(RB) void kpm_ranges_kernel(int N, int Lk, const uint8_t* mask,
+                                                        int64_t ld, int* kr, int* bad) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= N) return;
+  const uint8_t* mr = mask + (int64_t)r * ld;
+  int cnt = 0, first = Lk, last = -1;
+  for (int c = lane; c < Lk; c += 64)
+    if (mr[c] == 0) {
+      ++cnt;
+      first = min(first, c);
+      last = max(last, c);
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    cnt += __shfl_xor(cnt, o, 64);
+    first = min(first, __shfl_xor(first, o, 64));
+    last = max(last, __shfl_xor(last, o, 64));
+  }
+  if (lane == 0) {
+    const bool ok = cnt > 0 && last - first + 1 == cnt;
+    kr[2 * r] = cnt > 0 ? first : 0;
+    kr[2 * r + 1] = last + 1;
+    if (!ok) atomicAdd(bad, 1);
+  }
+}
+
 template <typename TP, typename TS>
 __global__ __launch_bounds__(RB) void softmax_bwd_kernel(int64_t rows, int n, const TP* p,
                                                          int64_t ldp, const float* dp,
@@ -1019,6 +1078,32 @@ extern "C" int jmt_softmax_fwd(int p_dt, int64_t rows, int n, const float* s, in
       hipLaunchKernelGGL((softmax_fwd_kernel<TP>), dim3(row_blocks(rows)), dim3(RB), 0, st, rows,
                          n, s, lds, scale, (TP*)p, ldp));
   JMT_LAUNCH_CHECK("jmt_softmax_fwd");
+  return JMT_OK;
+}
+
+extern "C" int jmt_softmax_fwd_kr(int p_dt, int64_t rows, int n, const float* s, int64_t lds,
+                                  float scale, void* p, int64_t ldp, const int* kr, int kr_mod,
+                                  int64_t rows_per_seq, void* stream) {
+  if (rows == 0) return JMT_OK;
+  JMT_CHECK_ARG(n > 0 && ldp >= n && s && p, "jmt_softmax_fwd_kr: bad args");
+  JMT_CHECK_ARG(kr != nullptr && kr_mod >= 1 && rows_per_seq >= 1 && rows % rows_per_seq == 0 &&
+                    (rows / rows_per_seq) % kr_mod == 0,
+                "jmt_softmax_fwd_kr: needs a table, kr_mod >= 1 dividing rows / rows_per_seq");
+  hipStream_t st = as_stream(stream);
+  JMT_DISPATCH1(p_dt, TP,
+      hipLaunchKernelGGL((softmax_fwd_kr_kernel<TP>), dim3(row_blocks(rows)), dim3(RB), 0, st,
+                         rows, n, s, lds, scale, (TP*)p, ldp, kr, kr_mod, rows_per_seq));
+  JMT_LAUNCH_CHECK("jmt_softmax_fwd_kr");
+  return JMT_OK;
+}
+
+extern "C" int jmt_kpm_ranges(int N, int Lk, const void* mask, int64_t ld, int* kr, int* bad,
+                              void* stream) {
+  if (N == 0) return JMT_OK;
+  JMT_CHECK_ARG(N > 0 && Lk > 0 && ld >= Lk && mask && kr && bad, "jmt_kpm_ranges: bad args");
+  hipLaunchKernelGGL(kpm_ranges_kernel, dim3(row_blocks(N)), dim3(RB), 0, as_stream(stream), N, Lk,
+                     (const uint8_t*)mask, ld, kr, bad);
+  JMT_LAUNCH_CHECK("jmt_kpm_ranges");
   return JMT_OK;
 }
 

@@ -120,6 +120,32 @@ _PROTOS = {
                                  c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
                                  c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_int,
                                  C.POINTER(c_int), c_int, c_int, c_vp]),
+    # key ranges: the signatures without ranges + (kr, kr_mod) before the stream; jmt_attn_bwd_kr
+    # has no dq arguments (P / dS only); jmt_softmax_fwd_kr also takes rows_per_seq
+    "jmt_attn_fwd_kr": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
+                                c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_f,
+                                c_vp, c_vp, c_int, c_vp]),
+    "jmt_attn_fwd_sq_kr": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
+                                   c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                   c_f, c_vp, c_int, C.POINTER(c_int), c_int, c_vp, c_int, c_vp]),
+    "jmt_attn_bwd_kr": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
+                                c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
+                                c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_f, c_vp, c_int, c_vp]),
+    "jmt_attn_bwd_sq_kr": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
+                                   c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                   c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_f, c_int,
+                                   C.POINTER(c_int), c_int, c_vp, c_int, c_vp]),
+    "jmt_attn_short_fwd_kr": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                      c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                      c_i64, c_f, c_vp, c_vp, c_int, c_vp]),
+    "jmt_attn_short_bwd_kr": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                      c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                      c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
+                                      c_i64, c_i64, c_vp, c_i64, c_i64, c_f, c_vp, c_int, c_vp]),
+    "jmt_softmax_fwd_kr": (c_int, [c_int, c_i64, c_int, c_vp, c_i64, c_f, c_vp, c_i64, c_vp,
+                                   c_int, c_i64, c_vp]),
+    # (N, Lk, mask, ld, kr, bad, stream)
+    "jmt_kpm_ranges": (c_int, [c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
     # the tile (128 / 160 rows) jmt_attn_dkdv takes: (Lq, Lk, H, sdk_l, sdv_l, sdq_l, has_dq)
     "jmt_attn_dkdv_plan": (c_int, [c_int, c_int, c_int, c_i64, c_i64, c_i64, c_int]),
     # the kernels' ranges (no GPU call): (N, H, Lq, Lk, sk_l, sv_l), (N, H, Lq, Lk, ldp, sk_l,

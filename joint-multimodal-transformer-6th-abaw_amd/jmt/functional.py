@@ -731,6 +731,78 @@ def _round_up(a, b):
     return -(-a // b) * b
 
 
+class KeyRanges:
+    """A key padding mask as one run of valid keys per sequence: `table` is the device array of
+    int32 {kbeg, kend} pairs the *_kr kernels read (include/jmt.h), `B` its entries, `Lk` the
+    mask's key count.  Sequence n of a launch uses entry n % B, so the grouped launches (3 B and
+    6 B sequences) share the table of the B windows.  Built by key_ranges()."""
+    __slots__ = ("table", "B", "Lk")
+
+    def __init__(self, table, B, Lk):
+        self.table, self.B, self.Lk = table, B, Lk
+
+    @property
+    def op(self):
+        """(table, kr_mod): the `kr` operand of the ops.attn_* wrappers."""
+        return (self.table, self.B)
+
+
+_KR_PENDING = {}     # device -> int32 count of mask rows that were not one non-empty run
+
+
+def key_ranges(key_padding_mask) -> "KeyRanges":
+    """The KeyRanges of a (B, Lk) bool / uint8 key padding mask (True = ignore the key, torch's
+    convention), by one kernel (jmt_kpm_ranges; no torch op, so a captured step stays free of
+    torch kernels).  Padding is contiguous: every row must hold exactly one non-empty run of valid
+    keys (padded on the left, on the right or both).  A row without a valid key (torch returns NaN
+    there) or with a hole is counted on the device.  Eager: the count is read here (one host
+    read) and a non-zero count raises ValueError.  Under graph capture no host read is possible:
+    the count accumulates on the device and check_key_ranges() (or the next eager key_ranges call)
+    raises on it.  A KeyRanges passes through unchanged."""
+    m = key_padding_mask
+    if isinstance(m, KeyRanges):
+        return m
+    if not torch.is_tensor(m) or m.dtype not in (torch.bool, torch.uint8):
+        raise NotImplementedError("key_padding_mask: a bool (or uint8) mask or a KeyRanges; float "
+                                  "masks are not used on the JMT path")
+    if m.dim() != 2:
+        raise ValueError(f"key_padding_mask must be (N, Lk), got {tuple(m.shape)}")
+    dev = m.device
+    capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+    bad = _KR_PENDING.get(dev)
+    if bad is None:
+        if capturing:
+            raise RuntimeError("key_ranges under graph capture: run it once eagerly first (the "
+                               "bad-mask counter is allocated there)")
+        bad = _KR_PENDING[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    if m.stride(1) != 1:
+        m = m.contiguous()
+    B, Lk = m.shape
+    table = torch.empty(2 * B, dtype=torch.int32, device=dev)
+    ops.kpm_ranges(m, table, bad)
+    if not capturing:
+        check_key_ranges(dev)
+    return KeyRanges(table, B, Lk)
+
+
+def check_key_ranges(dev=None):
+    """Raise ValueError if a key_ranges call since the last check saw a mask row that is not one
+    non-empty run of valid keys (the count kept on the device while the step was replayed from a
+    graph); clears the count."""
+    devs = [dev] if dev is not None else list(_KR_PENDING)
+    n = 0
+    for d in devs:
+        bad = _KR_PENDING.get(d)
+        if bad is not None:
+            c = int(bad.item())
+            if c:
+                bad.zero_()
+            n += c
+    if n:
+        raise ValueError(f"key_padding_mask: {n} row(s) are not one non-empty run of valid keys "
+                         "(a row with every key masked, or valid keys that are not contiguous)")
+
+
 class AttnCoreFn(Function):
     """softmax(Q K^T / sqrt(dh)) V per (batch, head) — the core of F.multi_head_attention_forward
     (SURVEY.md §8a a6).  Q/K/V are column slices (qcol/kcol/vcol) of the in-projection outputs
@@ -742,9 +814,9 @@ class AttnCoreFn(Function):
     probabilities in the compute dtype."""
 
     @staticmethod
-    def _probs(q_src, k_src, E, H, qcol, kcol, ldS, scale, cd):
+    def _probs(q_src, k_src, E, H, qcol, kcol, ldS, scale, cd, kr=None):
         """P = softmax(scale Q K^T) as (N, H, Lq, ldS) in the compute dtype (score GEMM into fp32
-        + jmt_softmax_fwd)."""
+        + jmt_softmax_fwd; kr: over each sequence's key range, zero outside it)."""
         Lq, N = q_src.shape[0], q_src.shape[1]
         Lk = k_src.shape[0]
         dh = E // H
@@ -758,12 +830,12 @@ class AttnCoreFn(Function):
                  sB=(k_src.stride(1), dh),
                  c=[S.data_ptr()], ldc=ldS, sC=bS, batch0=N, batch1=H, device=dev)
         P = torch.empty(N * H * Lq * ldS, dtype=cd, device=dev)
-        ops.softmax_fwd(S, ldS, N * H * Lq, Lk, scale, P, ldS)
+        ops.softmax_fwd(S, ldS, N * H * Lq, Lk, scale, P, ldS, kr=kr, rows_per_seq=H * Lq)
         return P
 
     @staticmethod
-    def forward(ctx, q_src, k_src, v_src, E, H, qcol, kcol, vcol):
-        o, saved = attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol)
+    def forward(ctx, q_src, k_src, v_src, E, H, qcol, kcol, vcol, kr=None):
+        o, saved = attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, kr=kr)
         # which inputs are the same tensor (saved tensors are not guaranteed to unpack to the
         # same Python objects, so the aliasing is recorded here)
         owner = (0, 0 if k_src is q_src else 1,
@@ -796,7 +868,7 @@ class AttnCoreFn(Function):
                     bufs[i].zero_()
         attn_backward((tensors, meta), go, bufs[owner[0]], bufs[owner[1]], bufs[owner[2]])
         grads = [bufs[i] if owner[i] == i else None for i in range(3)]
-        return (*grads, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None)
 
 
 def _small_aligned(t, col, cd):
@@ -823,7 +895,9 @@ class AttnPlan(NamedTuple):
     the whole-row kernel.  bwd (None while the gradient buffers are unknown): "small" | "short" |
     "pds_dkdv" (P / dS kernel + attn_dkdv with dQ) | "bwd64_dkdv" (64-row backward with dQ +
     attn_dkdv) | "bwd64_gemm" (64-row backward + two batched GEMMs) | "gemm".  shared_q: the
-    *_sq launches take the call (whole-row forward and "pds_dkdv")."""
+    *_sq launches take the call (whole-row forward and "pds_dkdv").  With key ranges (kr) the
+    answers are "short", "fused" on the whole-row kernel (its backward must come out "pds_dkdv":
+    attn_backward raises otherwise) or "gemm": the kernels that take a range table."""
     fwd: str
     rows: bool
     bwd: Optional[str]
@@ -831,21 +905,32 @@ class AttnPlan(NamedTuple):
 
 
 # what attn_backward keeps of an attn_forward call besides its tensors (fwd: AttnPlan.fwd)
-AttnMeta = collections.namedtuple("AttnMeta", "E H qcol kcol vcol ldS scale cd fwd")
+# kr: the key range operand (table, kr_mod) of a call with ranges, else None
+AttnMeta = collections.namedtuple("AttnMeta", "E H qcol kcol vcol ldS scale cd fwd kr")
 
 
 def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=None,
-              fwd=None) -> AttnPlan:
+              fwd=None, kr=False) -> AttnPlan:
     """The one place an attention call's kernels are chosen (host only, no tensors).  q .. dv:
     AttnOperand of each view, the gradient ones (go: dO as attn_backward normalises it) once they
     exist.  fwd: the forward path already taken (attn_backward; the saved state fixes it).  The
     switches (ops._attn_fused / _attn_short / _attn_dkdv / _attn_pds, the library's forward-rows
-    switch) are read at every call and the kernels' ranges are asked of the library."""
+    switch) are read at every call and the kernels' ranges are asked of the library.  kr: the call
+    carries key ranges, which the small kernels, the 64-row forward and the 64-row backward do
+    not take."""
     dh = E // H
     half = cd != torch.float32
     if fwd is None:
         aligned = q.aligned and k.aligned and v.aligned and o.aligned
-        if aligned and ops.small_attn_ok(E, H, Lq, Lk):
+        if kr:
+            if half and aligned and ops.attn_short_ok(_dc(cd), dh, Lq, Lk):
+                fwd = "short"
+            elif (half and ops.attn_supported(_dc(cd), dh) and
+                  ops.attn_fwd_rows_ok(N, H, Lq, Lk, k.stride, v.stride)):
+                fwd = "fused"
+            else:
+                fwd = "gemm"
+        elif aligned and ops.small_attn_ok(E, H, Lq, Lk):
             fwd = "small"
         elif half and aligned and ops.attn_short_ok(_dc(cd), dh, Lq, Lk):
             fwd = "short"
@@ -872,11 +957,13 @@ def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=Non
     return AttnPlan(fwd, rows, bwd, rows and bwd == "pds_dkdv")
 
 
-def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
+def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None, kr=None):
     """softmax(Q K^T / sqrt(dh)) V on seq-first strided views (see AttnCoreFn).  Returns the
     output (Lq, N, E) (memory order of q_src's rows) and the state attn_backward needs.
     qshare = (spp, qtab): sequence p spp + b reads the Q rows of sequence qtab[p] spp + b
-    (ops.attn_fwd_sq; the caller has asked attn_plan with its gradient layouts)."""
+    (ops.attn_fwd_sq; the caller has asked attn_plan with its gradient layouts).
+    kr: a KeyRanges; sequence n attends to the keys of its entry n % kr.B only.  A call with
+    ranges never runs unmasked: attn_plan sends it to a kernel that takes the table."""
     cd = compute_dtype()
     for t in (q_src, k_src, v_src):
         assert t.dtype == cd and t.stride(-1) == 1
@@ -888,10 +975,18 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
     bS = (H * Lq * ldS, Lq * ldS)
     scale = 1.0 / math.sqrt(dh)
     o = Rows(q_src).like(E, cd)
+    if kr is not None:
+        if kr.Lk != Lk or N % kr.B:
+            raise ValueError(f"key ranges of a ({kr.B}, {kr.Lk}) mask on {N} sequences of {Lk} "
+                             "keys")
+        kr = kr.op
     plan = attn_plan(cd, N, H, Lq, Lk, E, _operand(q_src, qcol, cd), _operand(k_src, kcol, cd),
-                     _operand(v_src, vcol, cd), _operand(o, 0, cd))
+                     _operand(v_src, vcol, cd), _operand(o, 0, cd), kr=kr is not None)
     if qshare is not None and not (plan.fwd == "fused" and plan.rows):
         raise JMTError("attn_forward: qshare on an unsupported shape")
+    if kr is not None and (plan.fwd == "small" or (plan.fwd == "fused" and not plan.rows)):
+        raise JMTError(f"attn_forward: key ranges on a path that takes none ({plan.fwd})")
+    krk = {} if kr is None else {"kr": kr}
     if plan.fwd == "small":
         # short sequences (SELF_ATTEN head, intra-modal fusion): one wave per sequence, the
         # fp32 probabilities (N*H*Lq*Lk floats) kept for the backward (small_attn.hip)
@@ -914,10 +1009,10 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
                      _ptr(k_src, kcol), (k_src.stride(0), k_src.stride(1)),
                      _ptr(v_src, vcol), (v_src.stride(0), v_src.stride(1)),
                      o.data_ptr(), (o.stride(0), o.stride(1)), scale, lse,
-                     *(qshare if qshare is not None else ()))
+                     *(qshare if qshare is not None else ()), **krk)
         tensors = (q_src, k_src, v_src, None, o, lse)
     else:
-        P = AttnCoreFn._probs(q_src, k_src, E, H, qcol, kcol, ldS, scale, cd)
+        P = AttnCoreFn._probs(q_src, k_src, E, H, qcol, kcol, ldS, scale, cd, kr)
         ops.gemm(M=Lq, N=dh, K=Lk, ab_dtype=_dc(cd), c_dtype=_dc(cd),
                  a=[P.data_ptr()], lda=ldS, a_kmajor=True, sA=bS,
                  b=[_ptr(v_src, vcol)], ldb=v_src.stride(0), b_kmajor=False,
@@ -925,7 +1020,7 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None):
                  c=[o.data_ptr()], ldc=o.stride(0), sC=(o.stride(1), dh),
                  batch0=N, batch1=H, device=dev)
         tensors = (q_src, k_src, v_src, P, None, None)
-    return o, (tensors, AttnMeta(E, H, qcol, kcol, vcol, ldS, scale, cd, plan.fwd))
+    return o, (tensors, AttnMeta(E, H, qcol, kcol, vcol, ldS, scale, cd, plan.fwd, kr))
 
 
 def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
@@ -935,7 +1030,7 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
     dQ = dS_i K_i + dS_j K_j per shared query in its first use's rows of dq, the second use's
     rows left unwritten.  The path is attn_plan's answer for the buffers as they are handed in."""
     (q_src, k_src, v_src, *_), meta = saved
-    E, H, qcol, kcol, vcol, _, _, cd, fwd = meta
+    E, H, qcol, kcol, vcol, _, _, cd, fwd, kr = meta
     Lq, N = q_src.shape[0], q_src.shape[1]
     Lk = k_src.shape[0]
     v8 = _vec(cd)
@@ -946,7 +1041,11 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
     # decided again with the buffers at hand and the switches as they are now
     bwd = attn_plan(cd, N, H, Lq, Lk, E, _operand(q_src, qcol, cd), _operand(k_src, kcol, cd),
                     _operand(v_src, vcol, cd), None, _operand(go, 0, cd), _operand(dq, qcol, cd),
-                    _operand(dk, kcol, cd), _operand(dv, vcol, cd), fwd=fwd).bwd
+                    _operand(dk, kcol, cd), _operand(dv, vcol, cd), fwd=fwd,
+                    kr=kr is not None).bwd
+    if kr is not None and bwd not in ("short", "pds_dkdv", "gemm"):
+        raise JMTError("attn_backward: key ranges with buffers the P / dS + dK / dV / dQ kernels "
+                       f"do not take (attn_plan: {bwd})")
     if qshare is not None and bwd != "pds_dkdv":
         raise JMTError("attn_backward: qshare with buffers the P / dS + dK / dV / dQ kernels "
                        f"do not take (attn_plan: {bwd})")
@@ -971,7 +1070,8 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
 def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
     """The launches of attn_backward's path `bwd` (attn_plan) on normalised buffers."""
     (q_src, k_src, v_src, P, o, lse), meta = saved
-    E, H, qcol, kcol, vcol, ldS, scale, cd, _ = meta
+    E, H, qcol, kcol, vcol, ldS, scale, cd, _, kr = meta
+    krk = {} if kr is None else {"kr": kr}
     Lq, N = q_src.shape[0], q_src.shape[1]
     Lk = k_src.shape[0]
     dh = E // H
@@ -992,7 +1092,7 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
             ops.attn_short_bwd(_dc(cd), N, H, Lq, Lk, dh, go.data_ptr(), (so_l, so_n),
                                o.data_ptr(), (o.stride(0), o.stride(1)),
                                _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
-                               _ptr(v_src, vcol), (sv_l, sv_n), lse, *gouts, scale)
+                               _ptr(v_src, vcol), (sv_l, sv_n), lse, *gouts, scale, **krk)
         return
     if bwd in ("pds_dkdv", "bwd64_dkdv"):
         # P and dS (rows of 128-key tiles) -> dK = dS^T Q and dV = P^T dO in one persistent
@@ -1007,7 +1107,8 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
             ops.attn_bwd_sq(_dc(cd), N, H, Lq, Lk, dh, go.data_ptr(), (so_l, so_n),
                             o.data_ptr(), (o.stride(0), o.stride(1)),
                             _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
-                            _ptr(v_src, vcol), (sv_l, sv_n), lse, P, dS, ldp, scale, *qshare)
+                            _ptr(v_src, vcol), (sv_l, sv_n), lse, P, dS, ldp, scale, *qshare,
+                            **krk)
             ops.attn_dkdv_sq(_dc(cd), N, H, Lq, Lk, dh, P, dS, ldp, go.data_ptr(), (so_l, so_n),
                              _ptr(q_src, qcol), (sq_l, sq_n), _ptr(dk, kcol),
                              (dk.stride(0), dk.stride(1)), _ptr(dv, vcol),
@@ -1018,7 +1119,7 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
                      o.data_ptr(), (o.stride(0), o.stride(1)),
                      _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
                      _ptr(v_src, vcol), (sv_l, sv_n), lse, P, dS, ldp,
-                     *((None, (0, 0)) if pds else dq_args), scale)
+                     *((None, (0, 0)) if pds else dq_args), scale, **krk)
         ops.attn_dkdv(_dc(cd), N, H, Lq, Lk, dh, P, dS, ldp, go.data_ptr(), (so_l, so_n),
                       _ptr(q_src, qcol), (sq_l, sq_n), _ptr(dk, kcol),
                       (dk.stride(0), dk.stride(1)), _ptr(dv, vcol), (dv.stride(0), dv.stride(1)),
@@ -1064,27 +1165,29 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
              batch1=H, device=dev)
 
 
-def multihead_attention(query, key, value, in_w, in_b, out_w, out_b, num_heads):
+def multihead_attention(query, key, value, in_w, in_b, out_w, out_b, num_heads, kr=None):
     """nn.MultiheadAttention(E, H)(query, key, value) with dropout 0, seq-first (L, N, E).
     Every reference call site passes key is value: then K and V come from
-    one packed in_proj GEMM (and Q too for self-attention)."""
+    one packed in_proj GEMM (and Q too for self-attention).  kr: the KeyRanges of a
+    key_padding_mask."""
     E = in_w.shape[1]
     if query is key and key is value:
         qkv = linear(query, in_w, in_b, 0, 3 * E)
-        o = AttnCoreFn.apply(qkv, qkv, qkv, E, num_heads, 0, E, 2 * E)
+        o = AttnCoreFn.apply(qkv, qkv, qkv, E, num_heads, 0, E, 2 * E, kr)
     elif key is value:
         q = linear(query, in_w, in_b, 0, E)
         kv = linear(key, in_w, in_b, E, 2 * E)
-        o = AttnCoreFn.apply(q, kv, kv, E, num_heads, 0, 0, E)
+        o = AttnCoreFn.apply(q, kv, kv, E, num_heads, 0, 0, E, kr)
     else:
         q = linear(query, in_w, in_b, 0, E)
         k = linear(key, in_w, in_b, E, E)
         v = linear(value, in_w, in_b, 2 * E, E)
-        o = AttnCoreFn.apply(q, k, v, E, num_heads, 0, 0, 0)
+        o = AttnCoreFn.apply(q, k, v, E, num_heads, 0, 0, 0, kr)
     return linear(o, out_w, out_b)
 
 
-def multihead_attention_shared_query(query, keys, in_w, in_b, out_w, out_b, num_heads):
+def multihead_attention_shared_query(query, keys, in_w, in_b, out_w, out_b, num_heads,
+                                     kr=None):
     """[nn.MultiheadAttention(query, k, k) for k in keys] with ONE query projection: the
     reference applies each cross_attention_* module twice to the same query
     (mm_multi_transformers.py:142-167), so the q = query W_q^T + b_q GEMM is computed once."""
@@ -1093,7 +1196,7 @@ def multihead_attention_shared_query(query, keys, in_w, in_b, out_w, out_b, num_
     outs = []
     for key in keys:
         kv = linear(key, in_w, in_b, E, 2 * E)
-        o = AttnCoreFn.apply(q, kv, kv, E, num_heads, 0, 0, E)
+        o = AttnCoreFn.apply(q, kv, kv, E, num_heads, 0, 0, E, kr)
         outs.append(linear(o, out_w, out_b))
     return outs
 

@@ -271,11 +271,16 @@ class EncoderGroupFn(Function):
     one per t) — MultimodalTransformer_wo_JR feeds its encoders batch-first tensors
     (mm_transformers.py:119-122); the attention core is then one launch per group (a group's
     (B, T) rows are a (seq, batch)-strided layout, the G groups together are not), every GEMM,
-    LayerNorm and bias reduction stays one grouped launch."""
+    LayerNorm and bias reduction stays one grouped launch.
+    kr (meta): the KeyRanges of a (B, T) key padding mask; sequence g B + b of the one attention
+    launch uses entry b.  A mask over time has no meaning on the batch axis."""
 
     @staticmethod
     def forward(ctx, X, meta, *params):
-        H, eps1, eps2, batch_axis = meta
+        H, eps1, eps2, batch_axis, kr = meta
+        if kr is not None and batch_axis:
+            raise NotImplementedError("a key padding mask over time with attention over the "
+                                      "batch axis")
         cd = compute_dtype()
         X = _contig(X, cd)
         G, B, T, E = X.shape
@@ -295,7 +300,7 @@ class EncoderGroupFn(Function):
             asaved = [sv for _, sv in outs]
         else:
             sf = QKV.view(G * B, T, 3 * E).permute(1, 0, 2)      # (T, G*B, 3E) seq-first
-            o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E)  # memory (G*B, T, E)
+            o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, kr=kr)  # memory (G*B, T, E)
             O = o.permute(1, 0, 2)
         A1 = torch.empty(G, B, T, E, dtype=cd, device=dev)
         lg.fwd(lg.table(O, E) if batch_axis else lg.strided(O, E, R * E), R, col(2), col(3),
@@ -462,11 +467,12 @@ class EncoderGroupFn(Function):
         return (dX, None) + (None,) * len(params)
 
 
-def encoder_group(X, layers, num_heads: int, batch_axis: bool = False):
+def encoder_group(X, layers, num_heads: int, batch_axis: bool = False, kr=None):
     """Apply `layers` (one TransformerEncoderLayer per stream) to the stacked X (attention over
-    T, or over B with batch_axis)."""
+    T, or over B with batch_axis).  kr: the KeyRanges of a (B, T) key padding mask."""
     params = [p for layer in layers for p in encoder_layer_params(layer)]
-    meta = (num_heads, layers[0].layer_norm1.eps, layers[0].layer_norm2.eps, bool(batch_axis))
+    meta = (num_heads, layers[0].layer_norm1.eps, layers[0].layer_norm2.eps, bool(batch_axis),
+            kr)
     return EncoderGroupFn.apply(X, meta, *params)
 
 
@@ -501,11 +507,12 @@ def shared_query_table(pairs):
 class CrossAttention6Fn(Function):
     """The six key-is-value cross-attentions of mm_multi_transformers.py:142-167 on the stacked
     encoder outputs Y (3, B, T, E) -> O6 (6, B, T, E) in the reference's concatenation order
-    (CROSS_PAIRS).  params: 4 per module (mha_params) for cross_attention_v / _p / _pv."""
+    (CROSS_PAIRS).  params: 4 per module (mha_params) for cross_attention_v / _p / _pv.
+    kr (meta): the KeyRanges of a (B, T) key padding mask; sequence p B + b uses entry b."""
 
     @staticmethod
     def forward(ctx, Y, meta, *params):
-        H, pairs = meta
+        H, pairs, kr = meta
         cd = compute_dtype()
         Y = _contig(Y, cd)
         S, B, T, E = Y.shape
@@ -523,7 +530,8 @@ class CrossAttention6Fn(Function):
             # batch-major (NP * B, T, E) with row stride E
             oq, ok, ov = (_operand(sf, c, cd) for c in (0, E, 2 * E))
             od = AttnOperand(True, E)
-            if not attn_plan(cd, NP * B, H, T, T, E, oq, ok, ov, od, od, oq, ok, ov).shared_q:
+            if not attn_plan(cd, NP * B, H, T, T, E, oq, ok, ov, od, od, oq, ok, ov,
+                             kr=kr is not None).shared_q:
                 qtab = None
         # queries and packed key/values, one launch each.  Shared queries: the projection of the
         # first use only (the q columns of the other uses' rows of QKV stay unused); otherwise
@@ -538,7 +546,7 @@ class CrossAttention6Fn(Function):
         lg.fwd(lg.table([Y[k] for _, _, k in pairs], E), R, in_w, in_b,
                lg.strided((QKV, E), 3 * E, R * 3 * E), cd, E, 2 * E)
         qshare = (B, qtab) if qtab is not None else None
-        o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, qshare=qshare)
+        o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, qshare=qshare, kr=kr)
         O = o.permute(1, 0, 2)                                   # (NP*B, T, E) memory
         O6 = torch.empty(NP, B, T, E, dtype=cd, device=dev)
         lg.fwd(lg.strided(O, E, R * E), R, [M[m][2] for m, _, _ in pairs],
@@ -713,9 +721,9 @@ class CrossAttention6Fn(Function):
         return (dY, None) + (None,) * len(params)
 
 
-def cross_attention6(Y, modules, num_heads: int, pairs=CROSS_PAIRS):
+def cross_attention6(Y, modules, num_heads: int, pairs=CROSS_PAIRS, kr=None):
     params = [p for mod in modules for p in mha_params(mod)]
-    return CrossAttention6Fn.apply(Y, (num_heads, pairs), *params)
+    return CrossAttention6Fn.apply(Y, (num_heads, pairs, kr), *params)
 
 
 # ------------------------------------------------------------------------- concat head

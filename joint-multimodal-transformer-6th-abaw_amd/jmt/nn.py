@@ -58,7 +58,8 @@ class MultiheadAttention(nn.Module):
     """Drop-in for nn.MultiheadAttention(embed_dim, num_heads) with dropout 0, seq-first inputs
     and the packed `in_proj_weight` / `in_proj_bias` + `out_proj` parameters.  forward returns
     (attn_output, None): the head-averaged weights torch also returns are discarded by every
-    reference call site and are not materialised."""
+    reference call site and are not materialised.  key_padding_mask: contiguous
+    padding only (key ranges); attn_mask, is_causal and float masks raise."""
 
     def __init__(self, embed_dim: int, num_heads: int, dropout: float = 0.0, bias: bool = True):
         super().__init__()
@@ -81,10 +82,14 @@ class MultiheadAttention(nn.Module):
 
     def forward(self, query, key, value, key_padding_mask=None, need_weights=True,
                 attn_mask=None, average_attn_weights=True, is_causal=False):
-        if key_padding_mask is not None or attn_mask is not None or is_causal:
-            raise NotImplementedError("masks are not used on the JMT path")
+        if attn_mask is not None or is_causal:
+            raise NotImplementedError("attn_mask / is_causal are not used on the JMT path")
+        # a bool (N, Lk) mask (True = ignore, one run of valid keys per row) or the KeyRanges a
+        # caller built once for many modules (jmt.functional.key_ranges)
+        kr = F.key_ranges(key_padding_mask) if key_padding_mask is not None else None
         out = F.multihead_attention(query, key, value, self.in_proj_weight, self.in_proj_bias,
-                                    self.out_proj.weight, self.out_proj.bias, self.num_heads)
+                                    self.out_proj.weight, self.out_proj.bias, self.num_heads,
+                                    kr=kr)
         return out, None
 
 

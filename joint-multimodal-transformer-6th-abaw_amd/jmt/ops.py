@@ -470,9 +470,24 @@ def layernorm_bwd_grouped(X, R, dY, mean, rstd, gammas, dX, dgammas, dbetas, dsu
     return part
 
 
-def softmax_fwd(s, lds, rows, n, scale, p, ldp):
+def softmax_fwd(s, lds, rows, n, scale, p, ldp, kr=None, rows_per_seq=1):
+    """kr = (int32 {kbeg, kend} table, kr_mod): the softmax over each sequence's key range only
+    (row r belongs to sequence r // rows_per_seq), P zero outside it (jmt_softmax_fwd_kr)."""
+    if kr is not None:
+        _lib.call("jmt_softmax_fwd_kr", dt(p), rows, n, s.data_ptr(), lds, scale, p.data_ptr(),
+                  ldp, kr[0].data_ptr(), kr[1], rows_per_seq, stream())
+        return
     _lib.call("jmt_softmax_fwd", dt(p), rows, n, s.data_ptr(), lds, scale, p.data_ptr(), ldp,
               stream())
+
+
+def kpm_ranges(mask, kr, bad):
+    """Key range table of an (N, Lk) bool / uint8 key padding mask (True = ignore) into kr
+    (int32, 2 N); bad (int32, 1) += rows that are not one non-empty run of valid keys."""
+    N, Lk = mask.shape
+    assert mask.element_size() == 1 and mask.stride(1) == 1
+    _lib.call("jmt_kpm_ranges", N, Lk, mask.data_ptr(), mask.stride(0), kr.data_ptr(),
+              bad.data_ptr(), stream())
 
 
 def softmax_bwd(p, ldp, dp, lddp, rows, n, scale, ds, ldds):
@@ -497,25 +512,43 @@ def noop():
     _lib.call("jmt_noop", stream())
 
 
-def attn_fwd(dtype, N, H, Lq, Lk, dh, q_ptr, sq, k_ptr, sk, v_ptr, sv, o_ptr, so, scale, lse):
+def _kr_args(kr):
+    """(table pointer, kr_mod) of a key range operand kr = (int32 table, kr_mod), or ()."""
+    return () if kr is None else (kr[0].data_ptr(), kr[1])
+
+
+def attn_fwd(dtype, N, H, Lq, Lk, dh, q_ptr, sq, k_ptr, sk, v_ptr, sv, o_ptr, so, scale, lse,
+             kr=None):
     """Fused softmax(scale Q K^T) V + lse; sq/sk/sv/so = (row stride, batch stride) in
-    elements."""
-    launch = lambda: _lib.call("jmt_attn_fwd", dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
+    elements.  kr = (int32 {kbeg, kend} table, kr_mod): sequence n attends to keys
+    [kbeg, kend) of entry n % kr_mod only (jmt_attn_fwd_kr: the whole-row kernel)."""
+    name = "jmt_attn_fwd" if kr is None else "jmt_attn_fwd_kr"
+    launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
                                k_ptr, sk[0], sk[1], v_ptr, sv[0], sv[1], o_ptr, so[0], so[1],
-                               scale, lse.data_ptr() if lse is not None else None, stream())
+                               scale, lse.data_ptr() if lse is not None else None,
+                               *_kr_args(kr), stream())
     es = 4 if dtype == F32 else 2
     _hooked({"family": "attn_fwd", "flops": 4.0 * N * H * Lq * Lk * dh,
              "bytes": float(N * H) * ((2 * Lq + 2 * Lk) * dh * es + 4 * Lq)}, launch)
 
 
 def attn_bwd(dtype, N, H, Lq, Lk, dh, go_ptr, sgo, o_ptr, so, q_ptr, sq, k_ptr, sk, v_ptr, sv,
-             lse, p, ds, ldp, dq_ptr, sdq, scale):
+             lse, p, ds, ldp, dq_ptr, sdq, scale, kr=None):
     """P = exp(scale Q K^T - lse) and dS = scale P o (dO V^T - rowsum(dO o O)) written to p / ds
-    (ldp), dQ = dS K; dq_ptr None: P and dS only (the 128-row kernel; dQ from attn_dkdv)."""
-    launch = lambda: _lib.call("jmt_attn_bwd", dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0], sgo[1],
-                               o_ptr, so[0], so[1], q_ptr, sq[0], sq[1], k_ptr, sk[0], sk[1],
-                               v_ptr, sv[0], sv[1], lse.data_ptr(), p.data_ptr(), ds.data_ptr(),
-                               ldp, dq_ptr, sdq[0], sdq[1], scale, stream())
+    (ldp), dQ = dS K; dq_ptr None: P and dS only (the 128-row kernel; dQ from attn_dkdv).
+    kr: key ranges as attn_fwd (jmt_attn_bwd_kr: dq_ptr None only)."""
+    if kr is not None:
+        if dq_ptr is not None:
+            raise _lib.JMTError("attn_bwd: key ranges need the P / dS form (dq_ptr None)")
+        launch = lambda: _lib.call("jmt_attn_bwd_kr", dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
+                                   sgo[1], o_ptr, so[0], so[1], q_ptr, sq[0], sq[1], k_ptr, sk[0],
+                                   sk[1], v_ptr, sv[0], sv[1], lse.data_ptr(), p.data_ptr(),
+                                   ds.data_ptr(), ldp, scale, *_kr_args(kr), stream())
+    else:
+        launch = lambda: _lib.call("jmt_attn_bwd", dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
+                                   sgo[1], o_ptr, so[0], so[1], q_ptr, sq[0], sq[1], k_ptr, sk[0],
+                                   sk[1], v_ptr, sv[0], sv[1], lse.data_ptr(), p.data_ptr(),
+                                   ds.data_ptr(), ldp, dq_ptr, sdq[0], sdq[1], scale, stream())
     # algorithmic: two products per launch — dP and dQ, or (dq_ptr None) the S recompute and dP
     # (cdna_hip_programming.md counts the recompute as one of the backward's five products);
     # bytes: dO, O, Q, K, V, (dQ,) lse and the P / dS rows handed to attn_dkdv
@@ -583,26 +616,31 @@ def _qtab(qtab):
 
 
 def attn_fwd_sq(dtype, N, H, Lq, Lk, dh, q_ptr, sq, k_ptr, sk, v_ptr, sv, o_ptr, so, scale, lse,
-                spp, qtab):
-    """attn_fwd with shared queries (the whole-row kernel: Lq > 64)."""
+                spp, qtab, kr=None):
+    """attn_fwd with shared queries (the whole-row kernel: Lq > 64); kr: key ranges as attn_fwd
+    (jmt_attn_fwd_sq_kr)."""
     tab, npair = _qtab(qtab)
-    launch = lambda: _lib.call("jmt_attn_fwd_sq", dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
+    name = "jmt_attn_fwd_sq" if kr is None else "jmt_attn_fwd_sq_kr"
+    launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
                                k_ptr, sk[0], sk[1], v_ptr, sv[0], sv[1], o_ptr, so[0], so[1],
                                scale, lse.data_ptr() if lse is not None else None, spp, tab,
-                               npair, stream())
+                               npair, *_kr_args(kr), stream())
     es = 4 if dtype == F32 else 2
     _hooked({"family": "attn_fwd", "flops": 4.0 * N * H * Lq * Lk * dh, "shared_q": True,
              "bytes": float(N * H) * ((2 * Lq + 2 * Lk) * dh * es + 4 * Lq)}, launch)
 
 
 def attn_bwd_sq(dtype, N, H, Lq, Lk, dh, go_ptr, sgo, o_ptr, so, q_ptr, sq, k_ptr, sk, v_ptr, sv,
-                lse, p, ds, ldp, scale, spp, qtab):
-    """attn_bwd's P / dS form (dq_ptr None) with shared queries."""
+                lse, p, ds, ldp, scale, spp, qtab, kr=None):
+    """attn_bwd's P / dS form (dq_ptr None) with shared queries; kr: key ranges as attn_fwd
+    (jmt_attn_bwd_sq_kr)."""
     tab, npair = _qtab(qtab)
-    launch = lambda: _lib.call("jmt_attn_bwd_sq", dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
+    name = "jmt_attn_bwd_sq" if kr is None else "jmt_attn_bwd_sq_kr"
+    launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
                                sgo[1], o_ptr, so[0], so[1], q_ptr, sq[0], sq[1], k_ptr, sk[0],
                                sk[1], v_ptr, sv[0], sv[1], lse.data_ptr(), p.data_ptr(),
-                               ds.data_ptr(), ldp, scale, spp, tab, npair, stream())
+                               ds.data_ptr(), ldp, scale, spp, tab, npair, *_kr_args(kr),
+                               stream())
     es = 4 if dtype == F32 else 2
     lw = -(-Lk // 32) * 32
     _hooked({"family": "attn_bwd", "flops": 4.0 * N * H * Lq * Lk * dh, "shared_q": True,
@@ -641,23 +679,28 @@ _attn_short = {"on": os.environ.get("JMT_ATTN_SHORT", "1") != "0"}
 
 
 def attn_short_fwd(dtype, N, H, Lq, Lk, dh, q_ptr, sq, k_ptr, sk, v_ptr, sv, o_ptr, so, scale,
-                   lse):
-    """jmt_attn_fwd's result (o, lse) for Lq, Lk <= 32: one block per (n, h)."""
-    launch = lambda: _lib.call("jmt_attn_short_fwd", dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
+                   lse, kr=None):
+    """jmt_attn_fwd's result (o, lse) for Lq, Lk <= 32: one block per (n, h); kr: key ranges as
+    attn_fwd (jmt_attn_short_fwd_kr)."""
+    name = "jmt_attn_short_fwd" if kr is None else "jmt_attn_short_fwd_kr"
+    launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
                                k_ptr, sk[0], sk[1], v_ptr, sv[0], sv[1], o_ptr, so[0], so[1],
-                               scale, lse.data_ptr(), stream())
+                               scale, lse.data_ptr(), *_kr_args(kr), stream())
     es = 4 if dtype == F32 else 2
     _hooked({"family": "attn_short_fwd", "flops": 4.0 * N * H * Lq * Lk * dh,
              "bytes": float(N * H) * ((2 * Lq + 2 * Lk) * dh * es + 4 * Lq)}, launch)
 
 
 def attn_short_bwd(dtype, N, H, Lq, Lk, dh, go_ptr, sgo, o_ptr, so, q_ptr, sq, k_ptr, sk, v_ptr,
-                   sv, lse, dq_ptr, sdq, dk_ptr, sdk, dv_ptr, sdv, scale):
-    """dQ, dK, dV of attn_short_fwd in one kernel (P recomputed from lse; no P / dS in HBM)."""
-    launch = lambda: _lib.call("jmt_attn_short_bwd", dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
+                   sv, lse, dq_ptr, sdq, dk_ptr, sdk, dv_ptr, sdv, scale, kr=None):
+    """dQ, dK, dV of attn_short_fwd in one kernel (P recomputed from lse; no P / dS in HBM); kr:
+    the forward's key ranges (jmt_attn_short_bwd_kr)."""
+    name = "jmt_attn_short_bwd" if kr is None else "jmt_attn_short_bwd_kr"
+    launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
                                sgo[1], o_ptr, so[0], so[1], q_ptr, sq[0], sq[1], k_ptr, sk[0],
                                sk[1], v_ptr, sv[0], sv[1], lse.data_ptr(), dq_ptr, sdq[0], sdq[1],
-                               dk_ptr, sdk[0], sdk[1], dv_ptr, sdv[0], sdv[1], scale, stream())
+                               dk_ptr, sdk[0], sdk[1], dv_ptr, sdv[0], sdv[1], scale,
+                               *_kr_args(kr), stream())
     # algorithmic: dP, dQ, dK, dV (the P recompute is not counted); bytes: q, o, dO, k, v, lse
     # read, dq, dk, dv written
     es = 4 if dtype == F32 else 2

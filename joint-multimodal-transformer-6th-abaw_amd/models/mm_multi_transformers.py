@@ -44,9 +44,10 @@ class Attention(nn.Module):
 class SequentialEncoder(nn.Sequential):
     """mm_multi_transformers.py:29-33."""
 
-    def forward(self, x):
+    def forward(self, x, key_padding_mask=None):
+        # key_padding_mask (not in the reference): a (B, T) bool mask or its F.key_ranges
         for module in self._modules.values():
-            x = module(x)
+            x = module(x) if key_padding_mask is None else module(x, key_padding_mask)
         return x
 
 
@@ -61,16 +62,20 @@ class TransformerEncoderLayer(nn.Module):
         self.layer_norm1 = LayerNorm(input_dim)
         self.layer_norm2 = LayerNorm(input_dim)
 
-    def forward(self, x):
+    def forward(self, x, key_padding_mask=None):
+        # key_padding_mask (not in the reference): (N, L) bool, True = padded frame, or the
+        # KeyRanges a caller built once (F.key_ranges)
+        kr = F.key_ranges(key_padding_mask) if key_padding_mask is not None else None
         if grouped.enabled() and x.dim() == 3 and x.dtype == F.compute_dtype() and \
                 x.permute(1, 0, 2).is_contiguous():
             # seq-first view of a (N, L, E) buffer (the SELF_ATTEN head's token stack, the
             # ungrouped encoders): the grouped layer with one group — its backward accumulates
             # the residual and projection input gradients in place (no autograd gradient sums)
             Y = grouped.encoder_group(x.permute(1, 0, 2).unsqueeze(0), [self],
-                                      self.attention.num_heads)
+                                      self.attention.num_heads,
+                                      **({} if kr is None else {"kr": kr}))
             return Y.squeeze(0).permute(1, 0, 2)
-        attn_output, _ = self.attention(x, x, x)
+        attn_output, _ = self.attention(x, x, x, key_padding_mask=kr)
         x = self.layer_norm1(x, attn_output)
         ff_output = self.feed_forward(x)
         return self.layer_norm2(x, ff_output)
@@ -84,8 +89,8 @@ class TransformerEncoderBlock(nn.Module):
         self.layers = SequentialEncoder(
             *[TransformerEncoderLayer(input_dim, num_heads, hidden_dim) for _ in range(num_layers)])
 
-    def forward(self, x):
-        return self.layers(x)
+    def forward(self, x, key_padding_mask=None):
+        return self.layers(x, key_padding_mask)
 
 
 class MultimodalTransformer_w_JR(nn.Module):
@@ -94,6 +99,11 @@ class MultimodalTransformer_w_JR(nn.Module):
     forward(visual (B,T,512), physiological (B,T,512)):
       FC head         -> (T, B, 1024) seq-first (the reference's layout quirk, kept)
       SELF_ATTEN head -> (B, T, 512)
+    key_padding_mask (B, T) bool, True = padded frame (not in the reference, whose collate pads
+    short clips with zero frames that its attentions then attend to): converted to key ranges
+    once and used by the three encoders, every layer, and the six cross-attentions; the heads are
+    per frame and need none.  Outputs at padded frames are whatever the row-local layers make of
+    them (CCCLoss's `ignore` drops them).
     `final_encoder` (E=3072) is constructed and never called, as in the reference (:92-93)."""
 
     def __init__(self, visual_dim, audio_dim, num_heads, hidden_dim, num_layers,
@@ -122,9 +132,10 @@ class MultimodalTransformer_w_JR(nn.Module):
         else:
             raise NotImplementedError(output_format)
 
-    def forward(self, visual_features, physiological_features):
+    def forward(self, visual_features, physiological_features, key_padding_mask=None):
+        kr = F.key_ranges(key_padding_mask) if key_padding_mask is not None else None
         if grouped.enabled() and visual_features.shape == physiological_features.shape:
-            return self._forward_grouped(visual_features, physiological_features)
+            return self._forward_grouped(visual_features, physiological_features, kr)
         # cat + out_layer_pv as ONE K-concatenated GEMM (:120-124)
         joint_representation = F.linear((visual_features, physiological_features),
                                         self.out_layer_pv.weight, self.out_layer_pv.bias)
@@ -133,9 +144,9 @@ class MultimodalTransformer_w_JR(nn.Module):
         j = joint_representation.permute(1, 0, 2)
         dev = visual_features.device
         # the three encoders are independent: concurrent streams (:132-136)
-        v, p, j = streams.run_parallel([lambda: self.visual_encoder(v),
-                                        lambda: self.physiological_encoder(p),
-                                        lambda: self.joint_representation_encoder(j)], dev)
+        v, p, j = streams.run_parallel([lambda: self.visual_encoder(v, kr),
+                                        lambda: self.physiological_encoder(p, kr),
+                                        lambda: self.joint_representation_encoder(j, kr)], dev)
         taps.record("enc.visual_encoder", v, True)
         taps.record("enc.physiological_encoder", p, True)
         taps.record("enc.joint_representation_encoder", j, True)
@@ -145,7 +156,7 @@ class MultimodalTransformer_w_JR(nn.Module):
         def ca(mod, query, keys):
             return F.multihead_attention_shared_query(
                 query, keys, mod.in_proj_weight, mod.in_proj_bias, mod.out_proj.weight,
-                mod.out_proj.bias, mod.num_heads)
+                mod.out_proj.bias, mod.num_heads, **({} if kr is None else {"kr": kr}))
 
         r_v, r_p, r_pv = streams.run_parallel(
             [lambda: ca(self.cross_attention_v, v, (p, j)),
@@ -164,20 +175,21 @@ class MultimodalTransformer_w_JR(nn.Module):
         # FC head (:201-211): torch.cat of the 6 outputs never materialised (K-concat GEMM)
         return F.linear(tuple(outs), self.out_layer1.weight, self.out_layer1.bias)
 
-    def _forward_grouped(self, visual_features, physiological_features):
+    def _forward_grouped(self, visual_features, physiological_features, kr=None):
         """Same math, batched across the parallel branches (jmt/grouped.py): the three streams
         in one stacked (3, B, T, E) buffer — out_layer_pv's K-concatenated GEMM (:120-124)
         writing the joint representation into its third slot — each encoder layer of the three
         encoders as one grouped launch sequence, the six cross-attentions as one (:132-167)."""
         X = grouped.stack_joint(visual_features, physiological_features,
                                 self.out_layer_pv.weight, self.out_layer_pv.bias)
+        krk = {} if kr is None else {"kr": kr}      # without a mask: the calls of before
         for lv, lp, lj in zip(self.visual_encoder.layers, self.physiological_encoder.layers,
                               self.joint_representation_encoder.layers):
-            X = grouped.encoder_group(X, [lv, lp, lj], self.num_heads)
+            X = grouped.encoder_group(X, [lv, lp, lj], self.num_heads, **krk)
         taps.record_stacked(["enc.visual_encoder", "enc.physiological_encoder",
                              "enc.joint_representation_encoder"], X)
         O6 = grouped.cross_attention6(X, [self.cross_attention_v, self.cross_attention_p,
-                                          self.cross_attention_pv], self.num_heads)
+                                          self.cross_attention_pv], self.num_heads, **krk)
         taps.record_stacked([f"ca.{i}" for i in range(O6.shape[0])], O6)
         if self.output_format == "SELF_ATTEN":
             S, B, T, E = O6.shape

@@ -77,12 +77,22 @@ class Two_transformers(nn.Module):
         self.vregressor = MLP(dim, 128, digitize_num, dropout=v_dropout)
         self.aregressor = MLP(dim, 128, digitize_num, dropout=a_dropout)
 
-    def forward(self, f1_norm, f2_norm):
+    def forward(self, f1_norm, f2_norm, key_padding_mask=None):
+        # key_padding_mask (an extra keyword, default off): (B, T) bool, True = padded frame (the
+        # reference's collate left-pads short clips with zero frames and labels them -5.0); the
+        # time-axis attentions of the TRANSFORMER fusion then ignore those frames as keys
         video = F.l2_normalize(f2_norm)          # :118
         audio = F.l2_normalize(f1_norm)          # :119
         if self.linear is not None:
             video = self.linear(video)           # :120-121
-        av = self.mm_transformer(video, audio)
+        if key_padding_mask is None or self.joint_modalities == 'FC':    # 'FC': no attention
+            av = self.mm_transformer(video, audio)
+        elif self.joint_modalities == 'TRANSFORMER':
+            av = self.mm_transformer(video, audio, key_padding_mask=key_padding_mask)
+        else:
+            raise NotImplementedError("key_padding_mask with joint_modalities='NONE': its "
+                                      "self-attention runs over the batch axis, where a mask "
+                                      "over time has no meaning")
         taps.record("head", av, self.joint_modalities == 'TRANSFORMER' and
                     self.output_format == 'FC')
         # regressors in fp32 out (predictions feed the fp32 CCC statistics)
