@@ -403,6 +403,51 @@ int jmt_attn_short_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const void*
                        int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n, float scale,
                        void* stream);
 
+/* Fused multi-head attention, head dims 64 and 128 (num_heads 8 and 4 at E = 512; added to ABI 7,
+ * nothing else changes): a flash-attention forward and a backward that keeps only lse, with the
+ * element addressing of jmt_attn_* (seq-first strided views, head h at columns h*dh, lse float at
+ * (n*H + h)*Lq + q).  Rows 16-B aligned, strides non-negative multiples of 8 elements.
+ * jmt_attn_mh_ok(dt, dh, N, H, Lq, Lk, sq_l, sk_l, sv_l) != 0 for what the kernels take: dt
+ *   bf16 / fp16, dh 64 or 128, N, H >= 1, 1 <= Lq, Lk <= 2^20, N*H*ceil(Lq/64) and
+ *   N*H*ceil(Lk/64) (the grids: one block per 64-row item) <= 2^31 - 1, row strides <= 2^31 - 1
+ *   (every element offset is formed in 64 bits).  Anything else returns JMT_ERR_UNSUPPORTED
+ *   before a launch; null / misaligned pointers, bad strides and bad range tables JMT_ERR_ARG;
+ *   N == 0 or Lq == 0 JMT_OK without a launch.  dh = 256 and dh < 64 have no fused kernel.
+ * jmt_attn_mh_fwd: o = softmax(scale Q K^T) V in the compute dtype and lse (may be NULL); each
+ *   query row's result depends on that row and the keys only.
+ * jmt_attn_mh_bwd: two stream-ordered kernels, no atomics (bitwise reproducible), no P / dS in
+ *   memory: dq = dS K and delta = rowsum(dO o O) (from the 16-bit o) into `delta` (N*H*Lq floats,
+ *   caller-owned workspace, laid out like lse), then dk = dS^T Q and dv = P^T dO, with
+ *   P = exp(scale Q K^T - lse) and dS = scale P o (dO V^T - delta) rounded to the compute dtype.
+ *   dq / dk / dv are overwritten and may be column slices of one buffer.
+ * jmt_attn_mh_fwd_kr / jmt_attn_mh_bwd_kr: key ranges as above (keys outside the range:
+ *   probability exactly 0, their K / V rows are not read, dk / dv rows exact zeros; key tiles
+ *   wholly outside the range are skipped; an empty range gives o = 0).  With every entry
+ *   {0, Lk} the results are bitwise those of the plain forms. */
+int jmt_attn_mh_ok(int dt, int dh, int N, int H, int Lq, int Lk, int64_t sq_l, int64_t sk_l,
+                   int64_t sv_l);
+int jmt_attn_mh_fwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* q, int64_t sq_l,
+                    int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                    int64_t sv_l, int64_t sv_n, void* o, int64_t so_l, int64_t so_n, float scale,
+                    float* lse, void* stream);
+int jmt_attn_mh_fwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* q, int64_t sq_l,
+                       int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                       int64_t sv_l, int64_t sv_n, void* o, int64_t so_l, int64_t so_n,
+                       float scale, float* lse, const int* kr, int kr_mod, void* stream);
+int jmt_attn_mh_bwd(int dt, int N, int H, int Lq, int Lk, int dh, const void* go, int64_t sgo_l,
+                    int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n, const void* q,
+                    int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                    const void* v, int64_t sv_l, int64_t sv_n, const float* lse, void* dq,
+                    int64_t sdq_l, int64_t sdq_n, void* dk, int64_t sdk_l, int64_t sdk_n, void* dv,
+                    int64_t sdv_l, int64_t sdv_n, float scale, float* delta, void* stream);
+int jmt_attn_mh_bwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                       int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n,
+                       const void* q, int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                       int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n, const float* lse,
+                       void* dq, int64_t sdq_l, int64_t sdq_n, void* dk, int64_t sdk_l,
+                       int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n, float scale,
+                       float* delta, const int* kr, int kr_mod, void* stream);
+
 /* Attention over short sequences (Lq, Lk <= 8; E = H*dh = 512, E/8/H a power of two, dt any of
  * fp32/bf16/fp16): the SELF_ATTEN head's 6-token sequences (mm_multi_transformers.py:169-199)
  * and intra-modal fusion's 2-token ones (intra_modal_transformer_fusion.py:93-108), same element

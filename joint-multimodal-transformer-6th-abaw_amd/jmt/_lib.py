@@ -142,6 +142,25 @@ _PROTOS = {
                                       c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                                       c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
                                       c_i64, c_i64, c_vp, c_i64, c_i64, c_f, c_vp, c_int, c_vp]),
+    # fused multi-head attention (dh 64 / 128): (dt, dh, N, H, Lq, Lk, sq_l, sk_l, sv_l); the
+    # forward as jmt_attn_short_fwd(_kr); the backward as jmt_attn_short_bwd(_kr) + the delta
+    # workspace after the scale
+    "jmt_attn_mh_ok": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64]),
+    "jmt_attn_mh_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
+                                c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                c_f, c_vp, c_vp]),
+    "jmt_attn_mh_fwd_kr": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                   c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                   c_i64, c_f, c_vp, c_vp, c_int, c_vp]),
+    "jmt_attn_mh_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_i64,
+                                c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                c_i64, c_vp, c_i64, c_i64, c_f, c_vp, c_vp]),
+    "jmt_attn_mh_bwd_kr": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                   c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                   c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
+                                   c_i64, c_i64, c_vp, c_i64, c_i64, c_f, c_vp, c_vp, c_int,
+                                   c_vp]),
     "jmt_softmax_fwd_kr": (c_int, [c_int, c_i64, c_int, c_vp, c_i64, c_f, c_vp, c_i64, c_vp,
                                    c_int, c_i64, c_vp]),
     # (N, Lk, mask, ld, kr, bad, stream)

@@ -891,13 +891,15 @@ def _operand(t, col, cd) -> AttnOperand:
 
 
 class AttnPlan(NamedTuple):
-    """fwd: "small" | "short" | "fused" | "gemm" (GEMM + softmax).  rows: the fused forward is
-    the whole-row kernel.  bwd (None while the gradient buffers are unknown): "small" | "short" |
-    "pds_dkdv" (P / dS kernel + attn_dkdv with dQ) | "bwd64_dkdv" (64-row backward with dQ +
-    attn_dkdv) | "bwd64_gemm" (64-row backward + two batched GEMMs) | "gemm".  shared_q: the
-    *_sq launches take the call (whole-row forward and "pds_dkdv").  With key ranges (kr) the
-    answers are "short", "fused" on the whole-row kernel (its backward must come out "pds_dkdv":
-    attn_backward raises otherwise) or "gemm": the kernels that take a range table."""
+    """fwd: "small" | "short" | "fused" | "mh" (the fused multi-head kernels, head dim 64 or
+    128) | "gemm" (GEMM + softmax).  rows: the fused forward is the whole-row kernel (False for
+    "mh").  bwd (None while the gradient buffers are unknown): "small" | "short" | "pds_dkdv"
+    (P / dS kernel + attn_dkdv with dQ) | "bwd64_dkdv" (64-row backward with dQ + attn_dkdv) |
+    "bwd64_gemm" (64-row backward + two batched GEMMs) | "mh" (whenever the forward ran "mh") |
+    "gemm".  shared_q: the *_sq launches take the call (whole-row forward and "pds_dkdv"; never
+    "mh").  With key ranges (kr) the answers are "short", "fused" on the whole-row kernel (its
+    backward must come out "pds_dkdv": attn_backward raises otherwise), "mh" or "gemm": the
+    kernels that take a range table."""
     fwd: str
     rows: bool
     bwd: Optional[str]
@@ -914,7 +916,7 @@ def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=Non
     """The one place an attention call's kernels are chosen (host only, no tensors).  q .. dv:
     AttnOperand of each view, the gradient ones (go: dO as attn_backward normalises it) once they
     exist.  fwd: the forward path already taken (attn_backward; the saved state fixes it).  The
-    switches (ops._attn_fused / _attn_short / _attn_dkdv / _attn_pds, the library's forward-rows
+    switches (ops._attn_fused / _attn_short / _attn_mh / _attn_dkdv / _attn_pds, the library's forward-rows
     switch) are read at every call and the kernels' ranges are asked of the library.  kr: the call
     carries key ranges, which the small kernels, the 64-row forward and the 64-row backward do
     not take."""
@@ -922,12 +924,17 @@ def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=Non
     half = cd != torch.float32
     if fwd is None:
         aligned = q.aligned and k.aligned and v.aligned and o.aligned
+        # the multi-head kernels: asked last, after "small", "short" and "fused" have declined
+        mh = lambda: (half and aligned and
+                      ops.attn_mh_ok(_dc(cd), dh, N, H, Lq, Lk, q.stride, k.stride, v.stride))
         if kr:
             if half and aligned and ops.attn_short_ok(_dc(cd), dh, Lq, Lk):
                 fwd = "short"
             elif (half and ops.attn_supported(_dc(cd), dh) and
                   ops.attn_fwd_rows_ok(N, H, Lq, Lk, k.stride, v.stride)):
                 fwd = "fused"
+            elif mh():
+                fwd = "mh"
             else:
                 fwd = "gemm"
         elif aligned and ops.small_attn_ok(E, H, Lq, Lk):
@@ -936,6 +943,8 @@ def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=Non
             fwd = "short"
         elif half and ops.attn_supported(_dc(cd), dh):
             fwd = "fused"
+        elif mh():
+            fwd = "mh"
         else:
             fwd = "gemm"
     rows = fwd == "fused" and ops.attn_fwd_rows_ok(N, H, Lq, Lk, k.stride, v.stride)
@@ -997,12 +1006,14 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None, kr=No
                            _ptr(v_src, vcol), (v_src.stride(0), v_src.stride(1)),
                            o.data_ptr(), (o.stride(0), o.stride(1)), scale, P)
         tensors = (q_src, k_src, v_src, P, None, None)
-    elif plan.fwd in ("short", "fused"):
+    elif plan.fwd in ("short", "fused", "mh"):
         # one kernel: scores stay on chip (attn.hip; Lq, Lk <= 32, the batch-axis attention of
         # wo_JR and the T = 16 real-data windows: one block per sequence, attn_short.hip); only
-        # lse is kept for the backward, which recomputes the probabilities
+        # lse is kept for the backward, which recomputes the probabilities ("mh": head dim 64 /
+        # 128, attn_mh.hip)
         lse = torch.empty(N * H * Lq, dtype=torch.float32, device=dev)
         (ops.attn_short_fwd if plan.fwd == "short" else
+         ops.attn_mh_fwd if plan.fwd == "mh" else
          ops.attn_fwd_sq if qshare is not None else ops.attn_fwd)(
                      _dc(cd), N, H, Lq, Lk, dh,
                      _ptr(q_src, qcol), (q_src.stride(0), q_src.stride(1)),
@@ -1043,7 +1054,7 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
                     _operand(v_src, vcol, cd), None, _operand(go, 0, cd), _operand(dq, qcol, cd),
                     _operand(dk, kcol, cd), _operand(dv, vcol, cd), fwd=fwd,
                     kr=kr is not None).bwd
-    if kr is not None and bwd not in ("short", "pds_dkdv", "gemm"):
+    if kr is not None and bwd not in ("short", "pds_dkdv", "mh", "gemm"):
         raise JMTError("attn_backward: key ranges with buffers the P / dS + dK / dV / dQ kernels "
                        f"do not take (attn_plan: {bwd})")
     if qshare is not None and bwd != "pds_dkdv":
@@ -1080,10 +1091,18 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
     sk_l, sk_n = k_src.stride(0), k_src.stride(1)
     sv_l, sv_n = v_src.stride(0), v_src.stride(1)
     so_l, so_n = go.stride(0), go.stride(1)
-    if bwd in ("small", "short"):
+    if bwd in ("small", "short", "mh"):
         gouts = [a for t, c in ((dq, qcol), (dk, kcol), (dv, vcol))
                  for a in (_ptr(t, c), (t.stride(0), t.stride(1)))]
-        if bwd == "small":
+        if bwd == "mh":
+            # P recomputed from lse in the dQ and in the dK / dV kernel (no P / dS in HBM);
+            # delta = rowsum(dO o O) passes from the first to the second through this workspace
+            delta = torch.empty(N * H * Lq, dtype=torch.float32, device=dev)
+            ops.attn_mh_bwd(_dc(cd), N, H, Lq, Lk, dh, go.data_ptr(), (so_l, so_n),
+                            o.data_ptr(), (o.stride(0), o.stride(1)),
+                            _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
+                            _ptr(v_src, vcol), (sv_l, sv_n), lse, *gouts, scale, delta, **krk)
+        elif bwd == "small":
             ops.small_attn_bwd(_dc(cd), N, H, Lq, Lk, E, go.data_ptr(), (so_l, so_n),
                                _ptr(q_src, qcol), (sq_l, sq_n), _ptr(k_src, kcol), (sk_l, sk_n),
                                _ptr(v_src, vcol), (sv_l, sv_n), P, *gouts, scale)

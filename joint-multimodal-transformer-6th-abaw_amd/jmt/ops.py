@@ -708,6 +708,50 @@ def attn_short_bwd(dtype, N, H, Lq, Lk, dh, go_ptr, sgo, o_ptr, so, q_ptr, sq, k
              "bytes": float(N * H) * ((4 * Lq + 4 * Lk) * dh * es + 4 * Lq)}, launch)
 
 
+# the fused multi-head kernels (attn_mh.hip: dh 64 / 128); JMT_ATTN_MH=0 keeps the GEMM + softmax
+# path for those head dims (A/B switch)
+_attn_mh = {"on": os.environ.get("JMT_ATTN_MH", "1") != "0"}
+
+
+def attn_mh_ok(dtype: int, dh: int, N: int, H: int, Lq: int, Lk: int, sq_l: int, sk_l: int,
+               sv_l: int) -> bool:
+    """Shapes the fused multi-head kernels cover (jmt_attn_mh_ok: 16-bit, dh 64 or 128, the
+    kernels' size and row stride limits); off with JMT_ATTN_FUSED=0 or JMT_ATTN_MH=0."""
+    return (_attn_fused["on"] and _attn_mh["on"] and
+            bool(_lib.load().jmt_attn_mh_ok(dtype, dh, N, H, Lq, Lk, sq_l, sk_l, sv_l)))
+
+
+def attn_mh_fwd(dtype, N, H, Lq, Lk, dh, q_ptr, sq, k_ptr, sk, v_ptr, sv, o_ptr, so, scale, lse,
+                kr=None):
+    """Flash-attention forward for dh 64 / 128 (o and lse; one block per 64 query rows of an
+    (n, h)); kr: key ranges as attn_fwd (jmt_attn_mh_fwd_kr)."""
+    name = "jmt_attn_mh_fwd" if kr is None else "jmt_attn_mh_fwd_kr"
+    launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
+                               k_ptr, sk[0], sk[1], v_ptr, sv[0], sv[1], o_ptr, so[0], so[1],
+                               scale, lse.data_ptr() if lse is not None else None,
+                               *_kr_args(kr), stream())
+    # bytes: q, k, v read, o and lse written
+    _hooked({"family": "attn_mh_fwd", "flops": 4.0 * N * H * Lq * Lk * dh,
+             "bytes": float(N * H) * ((2 * Lq + 2 * Lk) * dh * 2 + 4 * Lq)}, launch)
+
+
+def attn_mh_bwd(dtype, N, H, Lq, Lk, dh, go_ptr, sgo, o_ptr, so, q_ptr, sq, k_ptr, sk, v_ptr,
+                sv, lse, dq_ptr, sdq, dk_ptr, sdk, dv_ptr, sdv, scale, delta, kr=None):
+    """dQ, dK, dV of attn_mh_fwd: the dQ kernel (which also writes delta = rowsum(dO o O), N H Lq
+    floats) and the dK / dV kernel behind one entry point, P recomputed from lse in both, no
+    atomics; kr: the forward's key ranges (jmt_attn_mh_bwd_kr)."""
+    name = "jmt_attn_mh_bwd" if kr is None else "jmt_attn_mh_bwd_kr"
+    launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
+                               sgo[1], o_ptr, so[0], so[1], q_ptr, sq[0], sq[1], k_ptr, sk[0],
+                               sk[1], v_ptr, sv[0], sv[1], lse.data_ptr(), dq_ptr, sdq[0], sdq[1],
+                               dk_ptr, sdk[0], sdk[1], dv_ptr, sdv[0], sdv[1], scale,
+                               delta.data_ptr(), *_kr_args(kr), stream())
+    # algorithmic: the five products of a flash backward (S, dP, dV, dK, dQ); bytes: q, k, v, o,
+    # dO read, dq, dk, dv written, lse read, delta written
+    _hooked({"family": "attn_mh_bwd", "flops": 10.0 * N * H * Lq * Lk * dh,
+             "bytes": float(N * H) * ((4 * Lq + 4 * Lk) * dh * 2 + 8 * Lq)}, launch)
+
+
 SMALL_ATTN_MAX_L = 8
 
 
