@@ -109,6 +109,11 @@ int jmt_gemm(const jmt_gemm_desc* desc, void* stream);
  * problems (fp32 C) have no such operand. */
 int jmt_gemm_cin(const jmt_gemm_desc* desc, const void* const* c_in, int n_c_in, int64_t ldcin,
                  void* stream);
+/* the persistent configuration jmt_gemm would launch this descriptor on, with desc->splits as
+ * given (45: the ping-pong kernel; 0: another kernel, or a descriptor jmt_gemm refuses).
+ * Launches nothing.  A caller that wants a jmt_gemm_group16 launch to keep the bits of the
+ * launches it replaces asks this of every problem. */
+int jmt_gemm_persist_cfg(const jmt_gemm_desc* desc);
 size_t jmt_gemm_workspace_bytes(int M, int N, int batch, int splits);
 /* split-K factor jmt_gemm's planner picks for this problem (1 = no split).  jmt_gemm chooses the
  * block tile (128x128 or 256x256) from the same cost model: waves x (tile FLOPs / per-block MFMA
@@ -139,6 +144,27 @@ int jmt_gemm_grouped(const jmt_gemm_desc* descs, int n, void* workspace, size_t 
                      void* stream);
 size_t jmt_gemm_grouped_workspace_bytes(const jmt_gemm_desc* descs, int n);
 int jmt_gemm_grouped_plan(const jmt_gemm_desc* descs, int n, int* splits_out);
+
+/* Grouped 16-bit-C GEMMs (added to ABI 7, nothing else changes): up to 8 independent forward /
+ * input-gradient problems as the 256 x 256 tiles of ONE persistent ping-pong launch, for
+ * launches that sit next to each other and would each leave part of the chip idle.  No
+ * workspace.  Each problem is a jmt_gemm_desc with 16-bit A, B and C (one dtype and one
+ * majorness per group), M and N multiples of 256, K a multiple of 64 (>= 256), batch1 = 1,
+ * operand modes 0-3 as jmt_gemm defines them, bias per column (bias, or bias_tab with NULL
+ * entries allowed) or none, any alpha, beta = 0.  A problem's C has the bits of jmt_gemm on it
+ * alone on the ping-pong kernel.
+ * JMT_ERR_UNSUPPORTED before anything is launched (the caller runs jmt_gemm on each problem):
+ * fp32 operands or C, A row sums, split-K, a partial row panel or other sizes, bias per row,
+ * beta * C / relu / aux (one epilogue form per group: the plain one), mixed dtypes or layouts,
+ * more than 192 table pointers or 8192 bias floats in the group.  JMT_ERR_ARG: null or
+ * misaligned pointers, short tables, bad leading dimensions, C regions of two problems that
+ * overlap (disjoint column ranges of the same rows at one leading dimension do not).
+ * jmt_gemm_group16_ok runs the same checks and launches nothing. */
+int jmt_gemm_group16(const jmt_gemm_desc* descs, int n, void* stream);
+int jmt_gemm_group16_ok(const jmt_gemm_desc* descs, int n);
+/* development: at most `blocks` persistent blocks for the following jmt_gemm_group16 launches
+ * (0: one per CU), so that a block walks several items of a small group */
+void jmt_gemm_group16_set_grid(int blocks);
 
 /* ------------------------------------------------------------------ row-wise ops
  * Rows are `rows` vectors of length D at stride ld (elements). */

@@ -708,8 +708,10 @@ extern "C" size_t jmt_gemm_workspace_bytes(int M, int N, int batch, int splits) 
 
 // jmt_gemm (cin == false: the epilogue's beta * C operand is C) and jmt_gemm_cin (a table c_in
 // parallel to d->c with its own leading dimension) — the same launch, one load address apart
+// plan_out: nothing is launched; it receives the persistent configuration the launch would take
+// (persist_choice; 0: another kernel)
 static int gemm_run(const jmt_gemm_desc* d, bool cin, const void* const* c_in, int n_c_in,
-                    int64_t ldcin, void* stream) {
+                    int64_t ldcin, void* stream, int* plan_out = nullptr) {
   JMT_CHECK_ARG(d != nullptr, "jmt_gemm: null descriptor");
   const int dt = d->ab_dtype;
   JMT_CHECK_ARG(dt == JMT_F32 || dt == JMT_BF16 || dt == JMT_F16, "jmt_gemm: bad ab_dtype %d", dt);
@@ -849,6 +851,10 @@ static int gemm_run(const jmt_gemm_desc* d, bool cin, const void* const* c_in, i
   // persistent path (gemm_persist.hip: eligibility and the default choice live there)
   {
     const int pc = persist_choice(d, p, splits, cfg);
+    if (plan_out) {
+      *plan_out = pc;
+      return JMT_OK;
+    }
     if (pc) {
       p.tiles_m = (d->M + 255) / 256;                 // cfg 45: the last row panel may be partial
       p.tiles_n = d->N / 256;
@@ -925,6 +931,11 @@ extern "C" int jmt_gemm(const jmt_gemm_desc* d, void* stream) {
 extern "C" int jmt_gemm_cin(const jmt_gemm_desc* d, const void* const* c_in, int n_c_in,
                             int64_t ldcin, void* stream) {
   return gemm_run(d, true, c_in, n_c_in, ldcin, stream);
+}
+
+extern "C" int jmt_gemm_persist_cfg(const jmt_gemm_desc* d) {
+  int pc = 0;
+  return gemm_run(d, false, nullptr, 0, 0, nullptr, &pc) == JMT_OK ? pc : 0;
 }
 
 // ------------------------------------------------------------------ grouped weight gradients
@@ -1185,5 +1196,235 @@ extern "C" int jmt_gemm_grouped(const jmt_gemm_desc* descs, int n, void* workspa
     launch_group_reduce(g, rblk, st);
     JMT_LAUNCH_CHECK("jmt_gemm_grouped(reduce)");
   }
+  return JMT_OK;
+}
+
+// ------------------------------------------------------------------ grouped 16-bit-C GEMMs
+// jmt_gemm_group16 (gemm_persist.hip: Group16Src, gemm_group16_kernel): independent forward /
+// input-gradient problems that sit next to each other in the step as the items of one ping-pong
+// launch.  No planning: an item is one whole 256 x 256 tile of one problem, no workspace.
+namespace {
+
+int g_group16_grid = 0;     // development: jmt_gemm_group16_set_grid
+
+struct G16Plan {
+  int items, bias_floats;
+};
+
+// the rows of C entry `b` of problem d: first byte, bytes per row, row pitch in bytes
+struct G16Range {
+  uintptr_t lo, hi;
+  int64_t width, pitch;
+};
+
+G16Range g16_range(const jmt_gemm_desc& d, int b) {
+  const uintptr_t lo = d.c_mode == 1 ? (uintptr_t)d.c[b]
+                                     : (uintptr_t)d.c[0] + (uintptr_t)((int64_t)b * d.sC0 * 2);
+  G16Range r;
+  r.lo = lo;
+  r.width = (int64_t)d.N * 2;
+  r.pitch = d.ldc * 2;
+  r.hi = lo + (uintptr_t)((int64_t)(d.M - 1) * r.pitch + r.width);
+  return r;
+}
+
+// Two problems of one launch write concurrently.  Disjoint byte spans are; interleaved column
+// ranges of the same rows (one pitch: the query and the key / value columns of a packed buffer)
+// are when neither row reaches into the other's columns; anything else counts as an overlap.
+bool g16_overlap(const G16Range& x, const G16Range& y) {
+  if (x.hi <= y.lo || y.hi <= x.lo) return false;
+  if (x.pitch != y.pitch) return true;
+  const int64_t d = (int64_t)(((y.lo % (uintptr_t)x.pitch) + (uintptr_t)x.pitch -
+                               (x.lo % (uintptr_t)x.pitch)) % (uintptr_t)x.pitch);
+  return !(d >= x.width && d + y.width <= x.pitch);
+}
+
+int group16_check_one(const jmt_gemm_desc* d, const jmt_gemm_desc* d0, int i, int& pool,
+                      int& biasf) {
+#define JMT_G16_UNSUP(cond, ...) \
+  do { if (!(cond)) return set_error(JMT_ERR_UNSUPPORTED, __VA_ARGS__); } while (0)
+  const int dt = d->ab_dtype;
+  JMT_CHECK_ARG(dt == JMT_F32 || dt == JMT_BF16 || dt == JMT_F16,
+                "jmt_gemm_group16: problem %d: bad ab_dtype %d", i, dt);
+  JMT_G16_UNSUP(dt != JMT_F32 && d->c_dtype == dt,
+                "jmt_gemm_group16: problem %d: 16-bit A, B and C of one dtype only", i);
+  JMT_G16_UNSUP(dt == d0->ab_dtype && !d->a_kmajor == !d0->a_kmajor &&
+                    !d->b_kmajor == !d0->b_kmajor,
+                "jmt_gemm_group16: problem %d: one operand dtype and layout per group", i);
+  JMT_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "jmt_gemm_group16: problem %d: empty size", i);
+  JMT_G16_UNSUP(d->M % 256 == 0 && d->N % 256 == 0 && d->K % 64 == 0 && d->K >= 256,
+                "jmt_gemm_group16: problem %d: M and N must be multiples of 256 (no partial "
+                "row panel), K of 64 (>= 256)", i);
+  JMT_G16_UNSUP(d->n_dbias == 0, "jmt_gemm_group16: problem %d: A row sums", i);
+  JMT_G16_UNSUP(d->splits <= 1, "jmt_gemm_group16: problem %d: split-K", i);
+  JMT_G16_UNSUP(d->batch1 <= 1, "jmt_gemm_group16: problem %d: batch1 must be 1", i);
+  JMT_CHECK_ARG(d->n_bias >= 0 && d->n_bias <= MAXP,
+                "jmt_gemm_group16: problem %d: bias table size", i);
+  const bool bias = (d->bias != nullptr || d->n_bias > 0) && d->bias_mode != 0;
+  JMT_G16_UNSUP(!bias || d->bias_mode == 1, "jmt_gemm_group16: problem %d: bias per row", i);
+  // one compile-time epilogue form per launch, and the plain one is the only one compiled
+  JMT_G16_UNSUP(d->beta == 0.f && !d->relu && d->aux == nullptr,
+                "jmt_gemm_group16: problem %d: beta * C, relu and aux (the group's epilogue "
+                "form is alpha * acc + bias)", i);
+  const int batch0 = d->batch0 < 1 ? 1 : d->batch0;
+  JMT_CHECK_ARG(batch0 <= 65535, "jmt_gemm_group16: problem %d: batch too large", i);
+  JMT_CHECK_ARG(d->n_a >= 1 && d->n_a <= MAXP && d->n_b >= 1 && d->n_b <= MAXP && d->n_c >= 1 &&
+                    d->n_c <= MAXP, "jmt_gemm_group16: problem %d: pointer table size", i);
+  JMT_CHECK_ARG(d->a_mode >= 0 && d->a_mode <= 3 && d->b_mode >= 0 && d->b_mode <= 3 &&
+                    d->c_mode >= 0 && d->c_mode <= 1,
+                "jmt_gemm_group16: problem %d: bad operand mode", i);
+  JMT_CHECK_ARG(d->lda > 0 && d->ldb > 0 && d->ldc >= d->N && d->lda < (1LL << 31) &&
+                    d->ldb < (1LL << 31) && d->ldc < (1LL << 31) && d->lda % 8 == 0 &&
+                    d->ldb % 8 == 0 && d->ldc % 8 == 0 && d->sA0 % 8 == 0 && d->sB0 % 8 == 0 &&
+                    d->sC0 % 8 == 0 && d->sC0 >= 0,
+                "jmt_gemm_group16: problem %d: leading dimensions / strides (multiples of 8 "
+                "elements, ldc >= N, below 2^31)", i);
+  for (int k = 0; k < d->n_a; ++k)
+    JMT_CHECK_ARG(d->a[k] && ((uintptr_t)d->a[k] & 15) == 0,
+                  "jmt_gemm_group16: problem %d: A[%d] null or not 16-B aligned", i, k);
+  for (int k = 0; k < d->n_b; ++k)
+    JMT_CHECK_ARG(d->b[k] && ((uintptr_t)d->b[k] & 15) == 0,
+                  "jmt_gemm_group16: problem %d: B[%d] null or not 16-B aligned", i, k);
+  for (int k = 0; k < d->n_c; ++k)
+    JMT_CHECK_ARG(d->c[k] && ((uintptr_t)d->c[k] & 15) == 0,
+                  "jmt_gemm_group16: problem %d: C[%d] null or not 16-B aligned", i, k);
+  const int n_ab[2] = {d->n_a, d->n_b}, mode_ab[2] = {d->a_mode, d->b_mode};
+  const int kseg_ab[2] = {d->a_kseg, d->b_kseg};
+  for (int s = 0; s < 2; ++s) {
+    const char nm = s ? 'B' : 'A';
+    if (mode_ab[s] == 1)
+      JMT_CHECK_ARG(n_ab[s] >= batch0, "jmt_gemm_group16: problem %d: %c pointer table < batch0",
+                    i, nm);
+    if (mode_ab[s] >= 2) {
+      const int ks = kseg_ab[s];
+      JMT_CHECK_ARG(ks > 0 && ks % 64 == 0 &&
+                        (int64_t)n_ab[s] >= (int64_t)(mode_ab[s] == 3 ? batch0 : 1) *
+                                                ((d->K + ks - 1) / ks),
+                    "jmt_gemm_group16: problem %d: %c K-concat needs kseg a multiple of 64 and "
+                    "ceil(K / kseg) pointers (per batch entry in mode 3)", i, nm);
+    }
+  }
+  JMT_CHECK_ARG(d->n_c >= (d->c_mode == 1 ? batch0 : 1),
+                "jmt_gemm_group16: problem %d: C pointer table < batch0", i);
+  int nbias = 0;
+  if (bias) {
+    JMT_CHECK_ARG(d->n_bias == 0 || d->n_bias >= batch0,
+                  "jmt_gemm_group16: problem %d: bias table < batch0", i);
+    nbias = d->n_bias > 0 ? batch0 : 1;
+    for (int k = 0; k < nbias; ++k) {
+      const float* bp = d->n_bias > 0 ? d->bias_tab[k] : d->bias;
+      JMT_CHECK_ARG(((uintptr_t)bp & 3) == 0,
+                    "jmt_gemm_group16: problem %d: bias[%d] not 4-B aligned", i, k);
+    }
+    biasf += nbias * d->N;
+    JMT_G16_UNSUP(biasf <= kPersistBias,
+                  "jmt_gemm_group16: more than %d bias floats in the group", kPersistBias);
+  }
+  pool += d->n_a + d->n_b + d->n_c + nbias;
+  JMT_G16_UNSUP(pool <= G16_POOL, "jmt_gemm_group16: more than %d table pointers in the group",
+                G16_POOL);
+#undef JMT_G16_UNSUP
+  return JMT_OK;
+}
+
+int group16_plan(const jmt_gemm_desc* descs, int n, G16Plan& pl) {
+  JMT_CHECK_ARG(descs != nullptr, "jmt_gemm_group16: null descriptors");
+  JMT_CHECK_ARG(n >= 1 && n <= G16_MAXPROB, "jmt_gemm_group16: 1 to %d problems", G16_MAXPROB);
+  int pool = 0, biasf = 0;
+  long items = 0;
+  for (int i = 0; i < n; ++i) {
+    const int rc = group16_check_one(descs + i, descs, i, pool, biasf);
+    if (rc != JMT_OK) return rc;
+    const jmt_gemm_desc& d = descs[i];
+    items += (long)(d.M / 256) * (d.N / 256) * (d.batch0 < 1 ? 1 : d.batch0);
+  }
+  JMT_CHECK_ARG(items < (1L << 30), "jmt_gemm_group16: too many items");
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j) {
+      const jmt_gemm_desc &x = descs[i], &y = descs[j];
+      const int bx = x.batch0 < 1 ? 1 : x.batch0, by = y.batch0 < 1 ? 1 : y.batch0;
+      // whole problems first: their spans from the lowest entry to the highest
+      uintptr_t xlo = ~(uintptr_t)0, xhi = 0, ylo = ~(uintptr_t)0, yhi = 0;
+      for (int a = 0; a < bx; a += (x.c_mode == 1 || bx == 1) ? 1 : bx - 1) {
+        const G16Range r = g16_range(x, a);
+        xlo = r.lo < xlo ? r.lo : xlo;
+        xhi = r.hi > xhi ? r.hi : xhi;
+      }
+      for (int b = 0; b < by; b += (y.c_mode == 1 || by == 1) ? 1 : by - 1) {
+        const G16Range r = g16_range(y, b);
+        ylo = r.lo < ylo ? r.lo : ylo;
+        yhi = r.hi > yhi ? r.hi : yhi;
+      }
+      if (xhi <= ylo || yhi <= xlo) continue;
+      for (int a = 0; a < bx; ++a)
+        for (int b = 0; b < by; ++b)
+          JMT_CHECK_ARG(!g16_overlap(g16_range(x, a), g16_range(y, b)),
+                        "jmt_gemm_group16: C of problems %d (entry %d) and %d (entry %d) overlap",
+                        i, a, j, b);
+    }
+  pl.items = (int)items;
+  pl.bias_floats = biasf;
+  return JMT_OK;
+}
+
+}  // namespace
+
+extern "C" int jmt_gemm_group16_ok(const jmt_gemm_desc* descs, int n) {
+  G16Plan pl;
+  return group16_plan(descs, n, pl);
+}
+
+extern "C" void jmt_gemm_group16_set_grid(int blocks) { g_group16_grid = blocks; }
+
+extern "C" int jmt_gemm_group16(const jmt_gemm_desc* descs, int n, void* stream) {
+  G16Plan pl;
+  const int rc = group16_plan(descs, n, pl);
+  if (rc != JMT_OK) return rc;
+  Group16Params g = {};
+  g.nprob = n;
+  g.dbg = g_gemm_dbg;
+  int pool = 0, item = 0, biasf = 0;
+  for (int i = 0; i < n; ++i) {
+    const jmt_gemm_desc& d = descs[i];
+    Group16Prob& P = g.prob[i];
+    const int batch0 = d.batch0 < 1 ? 1 : d.batch0;
+    P.sA0 = d.a_mode == 3 ? (d.K + d.a_kseg - 1) / d.a_kseg : d.sA0;   // mode 3: segments per b0
+    P.sB0 = d.b_mode == 3 ? (d.K + d.b_kseg - 1) / d.b_kseg : d.sB0;
+    P.sC0 = d.sC0;
+    P.lda = (int)d.lda; P.ldb = (int)d.ldb; P.ldc = (int)d.ldc;
+    P.M = d.M; P.N = d.N; P.K = d.K;
+    P.batch0 = batch0;
+    P.tiles_m = d.M / 256;
+    P.tiles_n = d.N / 256;
+    P.a_mode = d.a_mode; P.b_mode = d.b_mode; P.c_mode = d.c_mode;
+    P.a_kseg = d.a_mode >= 2 ? d.a_kseg : 0;
+    P.b_kseg = d.b_mode >= 2 ? d.b_kseg : 0;
+    P.a_off = pool;
+    for (int k = 0; k < d.n_a; ++k) g.pool[pool++] = d.a[k];
+    P.b_off = pool;
+    for (int k = 0; k < d.n_b; ++k) g.pool[pool++] = d.b[k];
+    P.c_off = pool;
+    for (int k = 0; k < d.n_c; ++k) g.pool[pool++] = d.c[k];
+    const bool bias = (d.bias != nullptr || d.n_bias > 0) && d.bias_mode != 0;
+    P.bias_off = -1;
+    if (bias) {
+      P.bias_off = pool;
+      P.bias_n = d.n_bias > 0 ? batch0 : 0;
+      P.bias_lds = biasf;
+      if (d.n_bias > 0) for (int k = 0; k < batch0; ++k) g.pool[pool++] = d.bias_tab[k];
+      else g.pool[pool++] = d.bias;
+      biasf += (d.n_bias > 0 ? batch0 : 1) * d.N;
+    }
+    P.item0 = item;
+    item += P.tiles_m * P.tiles_n * batch0;
+    P.alpha = d.alpha;
+  }
+  g.W = item;
+  const int ncu = num_cus_persist();
+  int blocks = item < ncu ? item : ncu;
+  if (g_group16_grid > 0 && g_group16_grid < blocks) blocks = g_group16_grid;
+  launch_gemm_group16(g, descs[0].ab_dtype, descs[0].a_kmajor, descs[0].b_kmajor, biasf, blocks,
+                      as_stream(stream));
+  JMT_LAUNCH_CHECK("jmt_gemm_group16");
   return JMT_OK;
 }

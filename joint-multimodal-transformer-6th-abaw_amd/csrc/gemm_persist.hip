@@ -828,7 +828,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmParams p) {
 constexpr int P2_D = 10;
 static_assert(P2_D % 2 == 0 && P2_D <= 10, "pp2 deadline counts are derived for an even P2_D <= 10");
 
-// One schedule (pp2_run), two item sources.  The schedule owns the phases, the DMA stream, the
+// One schedule (pp2_run), three item sources.  The schedule owns the phases, the DMA stream, the
 // deadline counts, the accumulators and the order of everything; a source (Src) only says where
 // the block's items and their operands come from and what an item's epilogue stores:
 //   Item / Cursor, first() / next() / item()   the block's items w, w + G, w + 2 G, ...
@@ -842,7 +842,8 @@ static_assert(P2_D % 2 == 0 && P2_D <= 10, "pp2 deadline counts are derived for 
 //   epo()                                      the VMEM operations the deadlines count per epilogue
 //   epilogue(item, acc, rsum, smem, ...)       the item's stores
 // GemmSrc walks one GemmParams problem (cfg 45, and cfg 44 with SPL); GroupSrc walks the items of
-// several weight-gradient problems (jmt_gemm_grouped).  The vmcnt rule at the head of this file
+// several weight-gradient problems (jmt_gemm_grouped); Group16Src walks the whole tiles of several
+// forward / input-gradient problems with 16-bit C (jmt_gemm_group16).  The vmcnt rule at the head of this file
 // holds for any source whose epilogue issues AT LEAST epo() VMEM operations for every item,
 // whatever the item: vmcnt counts in issue order, so operations the count leaves out (GroupSrc's
 // beta * C and d[m] loads, or all of them under dbg 32) only make a deadline wait for more.
@@ -1380,6 +1381,161 @@ __global__ __launch_bounds__(256) void group_reduce_kernel(GroupParams g) {
   }
 }
 
+// ------------------------------------------------------------------ grouped 16-bit-C source
+// jmt_gemm_group16: the third source of pp2_run.  Logical item L of the launch belongs to the
+// problem p with prob[p].item0 <= L < prob[p + 1].item0; inside a problem the order is pwalk's
+// (column tile fastest, then row panel, then batch entry), so the column tiles of one A row panel
+// are consecutive and xcd_slot leaves them on one XCD.  There are no splits: an item is a whole
+// tile over the problem's whole K, contracted in GemmSrc's order through the same phases, and
+// the epilogue is persist_epilogue's plain form (EPI 0: alpha * acc + bias[n], paired 16-B
+// nontemporal stores) on the problem's own C, so a problem's C has the bits of jmt_gemm on it
+// alone under cfg 45.
+// Every item issues TM * TN / 2 16-B stores and no loads (the bias comes from LDS), whatever its
+// problem: the count the deadlines use; under dbg 32 it is 0 and every wait drains the stores.
+__device__ __forceinline__ GItem g16item(const Group16Params& g, int w) {
+  const int L = xcd_slot(w, g.W);
+  int pi = 0;
+  for (int i = 1; i < g.nprob; ++i) pi = L >= g.prob[i].item0 ? i : pi;
+  pi = __builtin_amdgcn_readfirstlane(pi);
+  const Group16Prob& P = g.prob[pi];
+  const int l = L - P.item0;
+  const int ntile = P.tiles_m * P.tiles_n;
+  const int b0 = l / ntile, t = l - b0 * ntile;
+  const int mt = t / P.tiles_n;
+  GItem it;
+  it.pi = pi;
+  it.m0 = mt * 256;
+  it.n0 = (t - mt * P.tiles_n) * 256;
+  it.b0 = b0;
+  it.sp = 0;
+  it.kt0 = 0;
+  it.len = P.K >> 6;
+  return it;
+}
+
+template <typename T>
+struct Group16Src {
+  using C = CfgPP;
+  using Item = GItem;
+  using Cursor = int;                                      // the item's index w in the launch
+  static constexpr bool CLAMP = false;                     // whole tiles only
+  static constexpr int NST = C::TM * (C::TN / 2);
+  const Group16Params& g;
+
+  __device__ __forceinline__ Cursor first() const { return blockIdx.x; }
+  __device__ __forceinline__ void next(Cursor& c) const { c += gridDim.x; }
+  __device__ __forceinline__ Item item(const Cursor& c) const { return g16item(g, c); }
+  __device__ __forceinline__ int ktiles(int nm) const {
+    int nT = 0;
+    for (int k = 0; k < nm; ++k) nT += g16item(g, blockIdx.x + k * gridDim.x).len;
+    return nT;
+  }
+  template <bool ISA, bool KM>
+  __device__ __forceinline__ PPOperand operand() const { return {0, 0, 0, 0}; }
+  // the operand follows the stream's current problem
+  template <bool ISA, bool KM>
+  __device__ __forceinline__ PPStream stream(const Item& it, int k0, PPOperand& o) const {
+    const Group16Prob& P = g.prob[it.pi];
+    const int mode = ISA ? P.a_mode : P.b_mode;
+    const int kseg = ISA ? P.a_kseg : P.b_kseg;
+    o = PPOperand::make<T, KM>(ISA ? P.lda : P.ldb, mode, kseg);
+    int kl;
+    const T* X = operand_base<T>(g.pool + (ISA ? P.a_off : P.b_off), mode, ISA ? P.sA0 : P.sB0,
+                                 0, it.b0, 0, kseg, k0, kl);
+    const int r0 = ISA ? it.m0 : it.n0;
+    PPStream s;
+    s.base = (const char*)(KM ? X + (int64_t)r0 * o.ld + kl : X + (int64_t)kl * o.ld + r0);
+    s.left = o.seg - (kl >> 6);
+    s.rmax = 256;
+    return s;
+  }
+  __device__ __forceinline__ int epo() const { return (g.dbg & 32) ? 0 : NST; }
+  // persist_epilogue<T, C, 0>'s arithmetic and stores on the item's problem
+  __device__ __forceinline__ void epilogue(const Item& cur, f32x4 (&acc)[C::TM][C::TN],
+                                           float (&)[2], const char* smem, int lane, int wm,
+                                           int wn) const {
+    const Group16Prob& P = g.prob[cur.pi];
+    T* const cp = P.c_mode == 1
+                      ? (T*)const_cast<void*>(g.pool[P.c_off + cur.b0])
+                      : (T*)const_cast<void*>(g.pool[P.c_off]) + (int64_t)cur.b0 * P.sC0;
+    const int gq = lane >> 4, rl = lane & 15;
+    float bias4[C::TN][4];
+    if (P.bias_off >= 0) {
+      const float* bl = (const float*)(smem + PP_NSLOT * PP_SLOT) + P.bias_lds +
+                        (P.bias_n > 0 ? cur.b0 * P.N : 0);
+#pragma unroll
+      for (int j = 0; j < C::TN; ++j) {
+        const f32x4 v = *(const f32x4*)(bl + cur.n0 + wn * C::WTN + 16 * j + 4 * gq);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bias4[j][e] = v[e];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < C::TN; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bias4[j][e] = 0.f;
+    }
+    const float alpha = P.alpha;
+    // the lane's store address for sub-tile row 0, sub-tile pair 0: row rl, its 8-column chunk
+    T* const cl = cp + (int64_t)(cur.m0 + wm * C::WTM + rl) * P.ldc + cur.n0 + wn * C::WTN +
+                  16 * (gq & 1) + 8 * (gq >> 1);
+#pragma unroll
+    for (int i = 0; i < C::TM; ++i) {
+      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+      u32x4 vj[C::TN / 2];
+#pragma unroll
+      for (int jp = 0; jp < C::TN / 2; ++jp) {
+        uint32_t pk[2][2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int j = 2 * jp + h;
+          float x[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) x[e] = acc[i][j][e] * alpha + bias4[j][e];
+#pragma unroll
+          for (int q = 0; q < 2; ++q) pk[h][q] = pack2<T>(x[2 * q], x[2 * q + 1]);
+        }
+        const auto r0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
+        const auto r1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
+        vj[jp] = u32x4{r0[0], r1[0], r0[1], r1[1]};
+      }
+      T* const crow = cl + (int64_t)(16 * i) * P.ldc;
+#pragma unroll
+      for (int jp = 0; jp < C::TN / 2; ++jp) {
+        JMT_DCHECK(cur.m0 + wm * C::WTM + 16 * i + rl < P.M &&
+                   cur.n0 + wn * C::WTN + 32 * jp + 16 * (gq & 1) + 8 * (gq >> 1) + 8 <= P.N &&
+                   cur.b0 < P.batch0);
+        __builtin_nontemporal_store(vj[jp], (u32x4*)(crow + 32 * jp));
+      }
+    }
+  }
+};
+
+template <typename T, bool AK, bool BK>
+__global__ __launch_bounds__(512) void gemm_group16_kernel(Group16Params g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* bias_lds = (float*)(smem + PP_NSLOT * PP_SLOT);
+  const int G = gridDim.x;
+  const int nm = (g.W - (int)blockIdx.x + G - 1) / G;
+  // every problem's per-column bias tables -> LDS, before any LDS-DMA is in flight
+  for (int pi = 0; pi < g.nprob; ++pi) {
+    const Group16Prob& P = g.prob[pi];
+    if (P.bias_off < 0) continue;
+    const int nb = (P.bias_n > 0 ? P.batch0 : 1) * P.N;
+    for (int i = threadIdx.x; i < nb; i += 512) {
+      const int b = i / P.N;
+      const float* bp = (const float*)g.pool[P.bias_off + b];
+      bias_lds[P.bias_lds + i] = bp ? bp[i - b * P.N] : 0.f;
+    }
+  }
+  __syncthreads();
+  if (nm <= 0) return;
+  const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const Group16Src<T> src{g};
+  if ((threadIdx.x >> 6) < 4) pp2_run<T, AK, BK, 0, 0>(src, lbase, smem, nm);
+  else pp2_run<T, AK, BK, 1, 0>(src, lbase, smem, nm);
+}
+
 // the persistent configuration (gemm_persist_kernel): cfg 40 = Cfg5's tile (128-B K-tiles, 2
 // stages).  (Cfg20's 64-B K-tiles in 4 stages with interleaved DMA issue — "cfg 41" — and a
 // three-deep A ring with the bias from scalar loads — "cfg 42" — measured slower on every step
@@ -1533,6 +1689,24 @@ void launch_gemm_group(const GroupParams& g, int dt, int ak, int bk, bool rs, in
 
 void launch_group_reduce(const GroupParams& g, int blocks, hipStream_t st) {
   hipLaunchKernelGGL(group_reduce_kernel, dim3(blocks), dim3(256), 0, st, g);
+}
+
+template <typename T, bool AK, bool BK>
+static void launch_group16_t(const Group16Params& g, int bias_floats, int blocks,
+                             hipStream_t st) {
+  void (*fn)(Group16Params) = gemm_group16_kernel<T, AK, BK>;
+  (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024);
+  const size_t lds = (size_t)PP_NSLOT * PP_SLOT + (size_t)bias_floats * sizeof(float);
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(512), lds, st, g);
+}
+
+void launch_gemm_group16(const Group16Params& g, int dt, int ak, int bk, int bias_floats,
+                         int blocks, hipStream_t st) {
+  for_layout(dt, ak, bk, [&](auto t, auto a, auto b) {
+    launch_group16_t<typename decltype(t)::type, decltype(a)::value, decltype(b)::value>(
+        g, bias_floats, blocks, st);
+  });
 }
 
 // cfg 44 eligibility (also the planner's split choice, pp_split_plan): 16-bit A / B, whole

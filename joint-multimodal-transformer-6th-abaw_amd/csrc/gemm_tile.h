@@ -748,4 +748,36 @@ void launch_gemm_group(const GroupParams& g, int dt, int ak, int bk, bool rs, in
                        hipStream_t st);
 void launch_group_reduce(const GroupParams& g, int blocks, hipStream_t st);
 
+// ------------------------------------------------------------------ grouped 16-bit-C GEMMs
+// jmt_gemm_group16: up to 8 forward / input-gradient problems (16-bit A, B and C, whole
+// 256 x 256 tiles, batch1 = 1, no split-K, the plain epilogue alpha * acc + bias[n]) as the
+// items of ONE ping-pong launch.  One record per problem and a shared pointer pool (A / B
+// tables or K-concat segments, C and per-column bias tables), read with scalar loads at an item
+// boundary; the bias tables of all problems are staged behind the slot ring, problem p's at
+// float offset bias_lds.
+constexpr int G16_MAXPROB = 8;
+constexpr int G16_POOL = 192;
+struct Group16Prob {
+  int64_t sA0, sB0, sC0;        // batch strides (mode 3: segments per batch entry, as GemmParams)
+  int lda, ldb, ldc;
+  int M, N, K;
+  int batch0, tiles_m, tiles_n;
+  int a_mode, b_mode, c_mode, a_kseg, b_kseg;
+  int a_off, b_off, c_off;      // first pool entry of each table
+  int bias_off, bias_n;         // bias_off < 0: no bias; bias_n == 0: one vector for every b0,
+                                // else pool[bias_off + b0] (a NULL entry adds nothing)
+  int bias_lds;
+  int item0;                    // first logical item of the launch (prefix of tiles x b0)
+  float alpha;
+};
+struct Group16Params {
+  Group16Prob prob[G16_MAXPROB];
+  const void* pool[G16_POOL];
+  int nprob, W, dbg, pad_;
+};
+static_assert(sizeof(Group16Params) <= 4096, "kernel arguments are limited to 4 KiB");
+// gemm_persist.hip: the launch; bias_floats = the staged tables of all problems
+void launch_gemm_group16(const Group16Params& g, int dt, int ak, int bk, int bias_floats,
+                         int blocks, hipStream_t st);
+
 }  // namespace jmt

@@ -59,6 +59,10 @@ _PROTOS = {
     "jmt_gemm_grouped": (c_int, [C.POINTER(GemmDesc), c_int, c_vp, C.c_size_t, c_vp]),
     "jmt_gemm_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(GemmDesc), c_int]),
     "jmt_gemm_grouped_plan": (c_int, [C.POINTER(GemmDesc), c_int, C.POINTER(c_int)]),
+    "jmt_gemm_group16": (c_int, [C.POINTER(GemmDesc), c_int, c_vp]),
+    "jmt_gemm_group16_ok": (c_int, [C.POINTER(GemmDesc), c_int]),
+    "jmt_gemm_group16_set_grid": (None, [c_int]),
+    "jmt_gemm_persist_cfg": (c_int, [C.POINTER(GemmDesc)]),
     # jmt_gemm with the beta * C operand read from a table parallel to desc.c (c_in, n, ldcin)
     "jmt_gemm_cin": (c_int, [C.POINTER(GemmDesc), c_vp, c_int, c_i64, c_vp]),
     "jmt_gemm_set_debug": (None, [c_int]),

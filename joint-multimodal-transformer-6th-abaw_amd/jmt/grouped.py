@@ -536,15 +536,18 @@ class CrossAttention6Fn(Function):
         # queries and packed key/values, one launch each.  Shared queries: the projection of the
         # first use only (the q columns of the other uses' rows of QKV stay unused); otherwise
         # each module's query projection is evaluated for both of its calls, as the reference does
+        # The two launches read Y and write disjoint columns of QKV: one grouped launch where
+        # lg.group16_scope takes them
         qkv = lg.strided(QKV, 3 * E, R * 3 * E)
-        if qtab is not None:
-            fu = [i for i, t in enumerate(qtab) if t == i]
-            lg.fwd(lg.table([Y[pairs[i][1]] for i in fu], E), R, [in_w[i] for i in fu],
-                   [in_b[i] for i in fu], lg.blocks([QKV[i] for i in fu], 3 * E), cd, 0, E)
-        else:
-            lg.fwd(lg.table([Y[q] for _, q, _ in pairs], E), R, in_w, in_b, qkv, cd, 0, E)
-        lg.fwd(lg.table([Y[k] for _, _, k in pairs], E), R, in_w, in_b,
-               lg.strided((QKV, E), 3 * E, R * 3 * E), cd, E, 2 * E)
+        with lg.group16_scope():
+            if qtab is not None:
+                fu = [i for i, t in enumerate(qtab) if t == i]
+                lg.fwd(lg.table([Y[pairs[i][1]] for i in fu], E), R, [in_w[i] for i in fu],
+                       [in_b[i] for i in fu], lg.blocks([QKV[i] for i in fu], 3 * E), cd, 0, E)
+            else:
+                lg.fwd(lg.table([Y[q] for _, q, _ in pairs], E), R, in_w, in_b, qkv, cd, 0, E)
+            lg.fwd(lg.table([Y[k] for _, _, k in pairs], E), R, in_w, in_b,
+                   lg.strided((QKV, E), 3 * E, R * 3 * E), cd, E, 2 * E)
         qshare = (B, qtab) if qtab is not None else None
         o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, qshare=qshare, kr=kr)
         O = o.permute(1, 0, 2)                                   # (NP*B, T, E) memory
@@ -712,11 +715,14 @@ class CrossAttention6Fn(Function):
                     lg.strided(dY[s], E), cd))
         # one launch per stream (600 128x128 tiles each, under one round of the chip's resident
         # slots): on their own streams the three overlap each other's last-round tails
+        # (default: the three write different dY[s] — one grouped launch where
+        # lg.group16_scope takes them, two rounds of the persistent grid instead of three)
         if _PAR_STREAM_DGRAD:
             streams.run_parallel(launches, dev)
         else:
-            for f in launches:
-                f()
+            with lg.group16_scope():
+                for f in launches:
+                    f()
         ctx.state = None
         return (dY, None) + (None,) * len(params)
 

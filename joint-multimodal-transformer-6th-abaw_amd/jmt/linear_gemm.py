@@ -129,6 +129,14 @@ def _weights(W, cd, r0: int):
                    tuple(Wc)), Kin, False
 
 
+# ------------------------------------------------------------------------- grouped launches
+def group16_scope():
+    """The fwd() / dgrad() calls inside — independent of each other — leave as one grouped launch
+    where ops.group16_scope takes them (16-bit, whole 256-row panels, each alone on the ping-pong
+    kernel), else exactly as they would outside; their operand tensors are kept until then."""
+    return ops.group16_scope()
+
+
 # ------------------------------------------------------------------------- forward
 def fwd(A: Operand, rows: int, W, b, C: Operand, cd, r0: int = 0, n=None, relu: bool = False):
     """C[g] = A[g] (rows x Kin) . W_g[r0:r0+n]^T + b_g[r0:r0+n] (relu).  W / b: one parameter
@@ -145,7 +153,8 @@ def fwd(A: Operand, rows: int, W, b, C: Operand, cd, r0: int = 0, n=None, relu: 
         kw["lda"] = F._vec(cd)
     ops.gemm(M=rows, N=n, K=Kin, ab_dtype=ops.dt(cd), c_dtype=ops.dt(C.owners[0]),
              a_kmajor=True, b_kmajor=True, batch0=1 if single else len(Bw.ptrs), bias_mode=1,
-             relu=relu, device=C.owners[0].device, **kw, **Bw.args("b"), **C.args("c"), **bias)
+             relu=relu, device=C.owners[0].device, keep=(*A.owners, *Bw.owners, *C.owners),
+             **kw, **Bw.args("b"), **C.args("c"), **bias)
 
 
 # ------------------------------------------------------------------------- input gradient
@@ -168,7 +177,8 @@ def dgrad(dY: Operand, rows: int, n: int, W, C: Operand, cd, r0: int = 0, kseg=N
             a = dY._replace(ptrs=dY.ptrs[c0:c0 + 8]) if dY.mode == KCAT else dY
             w = W._replace(ptrs=W.ptrs[c0:c0 + 8])
             ops.gemm(N=W.ld, K=len(w.ptrs) * W.kseg, a_kmajor=True, beta=beta if c0 == 0 else 1.0,
-                     **common, **a.args("a"), **w.args("b"), **C.args("c"))
+                     keep=(*a.owners, *w.owners, *C.owners), **common, **a.args("a"),
+                     **w.args("b"), **C.args("c"))
         return
     Bw, Kin, single = _weights(W, cd, r0)
     N = Kin if kseg is None or not single else kseg
@@ -188,8 +198,8 @@ def dgrad(dY: Operand, rows: int, n: int, W, C: Operand, cd, r0: int = 0, kseg=N
         else:
             cin = [c_in.data_ptr()]
     ops.gemm(N=N, K=n, a_kmajor=n != 1, batch0=nb, beta=beta, c_in=cin,
-             ldcin=C.ld if c_in is not None else 0, **common,
-             **kw, **Bw.args("b"), **C.args("c"))
+             ldcin=C.ld if c_in is not None else 0, keep=(*dY.owners, *Bw.owners, *C.owners),
+             **common, **kw, **Bw.args("b"), **C.args("c"))
 
 
 # ------------------------------------------------------------------------- weight gradient

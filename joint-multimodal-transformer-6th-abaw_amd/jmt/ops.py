@@ -72,7 +72,8 @@ def gemm(*, M: int, N: int, K: int, ab_dtype: int, c_dtype: int,
     with `done` may be held in the weight-gradient queue (wgrad_scope, or with defer=True /
     defer="late" — stage A / stage B below — until the end of the running backward pass) and
     flushed with its neighbours as one jmt_gemm_grouped launch; `keep` are the tensors its
-    operands live in."""
+    operands live in.  A launch without `done` issued inside a group16_scope is collected until
+    the scope's exit (one jmt_gemm_group16 launch, or this launch as it is), with its `keep`."""
     d = GemmDesc()
     d.ab_dtype, d.c_dtype = ab_dtype, c_dtype
     d.aux_dtype = dt(aux) if aux is not None else c_dtype
@@ -147,6 +148,11 @@ def gemm(*, M: int, N: int, K: int, ab_dtype: int, c_dtype: int,
 
     if done is not None and splits is None and _wgrad_enqueue(
             _WgradEntry(d, info, single, done, tuple(keep), device), defer):
+        return None
+    if done is None and _g16["depth"] > 0:
+        # (splits as single() would set them: what the group's checks and the planner see)
+        sp = splits if splits is not None else auto_splits(M, N, K, batch0 * batch1, ab_dtype)
+        _g16["ents"].append((d, info, single, sp, c_in is not None, tuple(keep)))
         return None
     ws = single()
     if done is not None:
@@ -376,6 +382,74 @@ def gemm_grouped(descs, device, splits_out=None):
     ws = workspace(nbytes, device)
     _lib.check(lib.jmt_gemm_grouped(arr, n, ws.data_ptr(), nbytes, stream()), "jmt_gemm_grouped")
     return ws
+
+
+# ------------------------------------------------------------------ grouped 16-bit-C GEMMs
+# Forward / input-gradient launches that sit next to each other and do not depend on each other
+# (the cross-attention block's query and key / value projections; its three stream gradients)
+# as ONE jmt_gemm_group16 launch: each alone leaves part of the persistent grid idle in its last
+# round and pays its own pipeline fill.  JMT_GEMM_GROUP16=0: every launch as before.
+_group16 = {"on": os.environ.get("JMT_GEMM_GROUP16", "1") != "0"}
+_g16 = {"depth": 0, "ents": []}
+
+
+def gemm_group16(descs, check_only: bool = False) -> int:
+    """jmt_gemm_group16 on GemmDesc structures, on the current stream; check_only: the code of
+    jmt_gemm_group16_ok, nothing is launched."""
+    lib = _lib.load()
+    n = len(descs)
+    arr = (GemmDesc * n)(*descs)
+    if check_only:
+        return int(lib.jmt_gemm_group16_ok(arr, n))
+    _lib.check(lib.jmt_gemm_group16(arr, n, stream()), "jmt_gemm_group16")
+    return _lib.OK
+
+
+class group16_scope:
+    """ops.gemm calls issued inside (forward / input-gradient launches: no `done`) are collected
+    and launched at the exit, on the stream current there: as one jmt_gemm_group16 launch when
+    the group takes them AND each of them alone would run unsplit on the ping-pong kernel
+    (jmt_gemm_persist_cfg == 45: the grouped launch then has the bits of the launches it
+    replaces); otherwise one by one, in the order and form they were issued in.  The calls must
+    not depend on each other's results."""
+
+    def __enter__(self):
+        _g16["depth"] += 1
+        return self
+
+    def __exit__(self, et, ev, tb):
+        _g16["depth"] -= 1
+        if _g16["depth"] == 0:
+            ents, _g16["ents"] = _g16["ents"], []
+            if et is None:
+                _group16_flush(ents)
+        return False
+
+
+def _group16_flush(ents) -> None:
+    if not ents:
+        return
+    lib = _lib.load()
+    n = len(ents)
+    ok = _group16["on"] and 2 <= n <= 8 and not any(e[4] for e in ents)
+    if ok:
+        for d, _, _, sp, _, _ in ents:
+            d.splits = sp
+            ok = ok and sp <= 1 and lib.jmt_gemm_persist_cfg(C.byref(d)) == 45
+    if ok:
+        arr = (GemmDesc * n)(*[e[0] for e in ents])
+        ok = lib.jmt_gemm_group16_ok(arr, n) == _lib.OK
+    if not ok:
+        for e in ents:
+            e[2]()
+        return
+    launch = lambda: _lib.check(lib.jmt_gemm_group16(arr, n, stream()), "jmt_gemm_group16")
+    if _launch_hook is not None:
+        info = dict(ents[0][1], grouped=n, flops=sum(e[1]["flops"] for e in ents),
+                    bytes=sum(e[1]["bytes"] for e in ents))
+        _launch_hook(info, launch)
+    else:
+        launch()
 
 
 # ------------------------------------------------------------------------------------ rows

@@ -32,7 +32,21 @@ BROKEN_GROUP = re.compile(r"gemm_group_kernel<bool _Accum, bool, E, (true|false)
 MANGLED_GROUP = re.compile(r"gemm_group_kernel.*?Lb([01])ELb([01])E")
 
 
+# the grouped 16-bit-C kernel (jmt_gemm_group16): forward / input-gradient problems, K-major A
+BROKEN_GROUP16 = re.compile(r"gemm_group16_kernel<bool _Accum, bool, E, (true|false)>")
+MANGLED_GROUP16 = re.compile(r"gemm_group16_kernel.*?Lb([01])ELb([01])E")
+
+
 def family(name: str):
+    if "gemm_group16_kernel" in name:
+        bs = BROKEN_GROUP16.search(name)
+        if bs:
+            return "gemm_NT" if bs.group(1) == "true" else "gemm_NN"
+        m = MANGLED_GROUP16.search(name)
+        if m:
+            return {("1", "1"): "gemm_NT", ("1", "0"): "gemm_NN", ("0", "0"): "gemm_TN",
+                    ("0", "1"): "gemm_TT"}[(m.group(1), m.group(2))]
+        return "gemm_?"
     if "gemm_group_kernel" in name:      # grouped weight gradients: MN-major A and B in the step
         bs = BROKEN_GROUP.search(name)
         if bs:
