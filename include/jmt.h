@@ -654,7 +654,12 @@ int jmt_amp_update(float* amp, float growth_factor, float backoff_factor, int gr
  *             bias corrections are 1.0 in fp32 long before)
  *   state[2]  step_size = lr / (1 - beta1^step)
  *   state[3]  bc2_sqrt  = sqrt(1 - beta2^step)
- *   state[4..7] reserved, zero
+ *   state[4]  clip coefficient c = min(1, max_norm / (norm + 1e-6))   (jmt_grad_norm writes it)
+ *   state[5]  L2 norm of the unscaled gradient                        (jmt_grad_norm writes it)
+ *   state[6]  max_norm, an input of jmt_grad_norm read on the device (write it between replays)
+ *   state[7]  reserved, zero
+ * Slots 4-6 belong to jmt_grad_norm and the *_clip entry points; every other entry point ignores
+ * them, and a block with zeros there (an older checkpoint) loads as before.
  * jmt_opt_tick (one thread; call it before jmt_adam_step): step += 1, then slots 2 and 3 in
  * double, rounded once to fp32; nothing happens when amp != NULL and amp[2] (found_inf) != 0.
  * The betas are doubles because torch forms 1 - beta and beta^step in Python doubles: a beta
@@ -681,6 +686,38 @@ int jmt_sgd_step_dev(int64_t n, float* param, float* grad, float* momentum_buf,
                      const float* state, float momentum, float dampening, float weight_decay,
                      int nesterov, int first_step, float grad_scale, const float* amp,
                      int zero_grad, void* shadow, int shadow_dt, void* stream);
+
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, L2, error_if_nonfinite=False) on the
+ * device state block above, additive to ABI 7.
+ * jmt_grad_norm: two launches.  A read-only pass squares and sums the flat fp32 gradient in
+ * double, one partial per chunk into `scratch`; a one-block fold adds the partials in a fixed
+ * order (no floating-point atomics: bitwise reproducible) and writes
+ *   state[5] = gs * sqrt(sum g^2)   gs = amp[1] when amp != NULL, else grad_scale; rounded once
+ *   state[4] = min(1, state[6] / (norm + 1e-6)) formed in double from the double norm, rounded
+ *              once; a NaN norm gives NaN, an infinite norm 0
+ * seg_off (int64[nseg + 1], device, ascending, within [0, n]; NULL with nseg = 0) cuts the buffer
+ * into segments (the parameters): seg_norm[s] (fp32[nseg], device) receives the unscaled norm of
+ * [seg_off[s], seg_off[s + 1]), and the total is the fixed-order sum of the segment sums, so it
+ * covers the segments only.  Segments that start on a multiple of 4 elements are read with 16-B
+ * loads.  nseg <= 2048.  scratch: jmt_grad_norm_scratch(n, nseg) bytes (-1 for arguments
+ * jmt_grad_norm refuses), 8-B aligned; grad 16-B aligned.
+ *
+ * jmt_adam_step_clip / jmt_sgd_step_dev_clip: jmt_adam_step / jmt_sgd_step_dev on c * grad with
+ * c = state[4]: the product is rounded to fp32 on its own before the existing arithmetic (gs,
+ * weight decay, ...), so the step equals, bit for bit, the unclipped step on fp32(c * grad). */
+int64_t jmt_grad_norm_scratch(int64_t n, int nseg);
+int jmt_grad_norm(int64_t n, const float* grad, float* state, double* scratch,
+                  int64_t scratch_bytes, const int64_t* seg_off, int nseg, float* seg_norm,
+                  float grad_scale, const float* amp, void* stream);
+int jmt_adam_step_clip(int64_t n, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
+                       float* max_exp_avg_sq, const float* state, double beta1, double beta2,
+                       float eps, float weight_decay, float grad_scale, const float* amp,
+                       int zero_grad, void* shadow, int shadow_dt, void* stream);
+int jmt_sgd_step_dev_clip(int64_t n, float* param, float* grad, float* momentum_buf,
+                          const float* state, float momentum, float dampening,
+                          float weight_decay, int nesterov, int first_step, float grad_scale,
+                          const float* amp, int zero_grad, void* shadow, int shadow_dt,
+                          void* stream);
 
 /* ------------------------------------------------------------------ validation post-processing
  * val.py:313-382 + EvaluationMetrics/cccmetric.py:4-21 on the GPU.

@@ -4,8 +4,12 @@
 //   jmt_adam_step     torch.optim.Adam / AMSGrad (L2 weight decay) over the flat fp32 buffers
 //   jmt_sgd_step_dev  sgd.hip's update with lr = state[0]
 // state (fp32[8], include/jmt.h): lr, step, step_size = lr / (1 - beta1^step),
-// bc2_sqrt = sqrt(1 - beta2^step), 4 reserved.  Both step kernels are pure streams: 16 B per lane
-// per array (8 B for the 16-bit shadow), grid-stride, scalar tail for n % 4.
+// bc2_sqrt = sqrt(1 - beta2^step), clip coefficient, gradient norm, max_norm (grad_norm.hip), 1
+// reserved.  Both step kernels are pure streams: 16 B per lane per array (8 B for the 16-bit
+// shadow), grid-stride, scalar tail for n % 4.
+//   jmt_adam_step_clip / jmt_sgd_step_dev_clip  the same kernels with CLIP: every gradient is
+//   first multiplied by c = state[4], a product rounded on its own, so that a clipped step on g
+//   is bit for bit the unclipped step on fp32(c g)
 #include "common.h"
 
 namespace jmt {
@@ -23,11 +27,19 @@ __global__ void opt_tick_kernel(float* st, double b1, double b2, const float* am
 
 struct AdamK {
   float w1, b2, w2, eps, wd, gs, step_size, bc2_sqrt;   // w1 = 1 - beta1, w2 = 1 - beta2
+  float c;                                              // CLIP: state[4]
 };
 
-template <bool AMS>
+// c g rounded once to fp32, never contracted into the multiply-adds that follow it
+__device__ __forceinline__ float clip_mul(float g, float c) {
+#pragma clang fp contract(off)
+  return __fmul_rn(g, c);
+}
+
+template <bool AMS, bool CLIP>
 __device__ __forceinline__ float adam_elem(float w, float g, float& m, float& v, float& vm,
                                            const AdamK& k) {
+  if constexpr (CLIP) g = clip_mul(g, k.c);
   g *= k.gs;
   if (k.wd != 0.f) g += k.wd * w;
   m = m + k.w1 * (g - m);
@@ -41,7 +53,7 @@ __device__ __forceinline__ float adam_elem(float w, float g, float& m, float& v,
   return w - k.step_size * (m / denom);
 }
 
-template <typename TS, bool AMS, bool ZG>
+template <typename TS, bool AMS, bool ZG, bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict__ p,
                                                    float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v,
@@ -53,7 +65,8 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict_
   typedef typename Frag16<TS>::h TS4;
   const bool skip = amp && amp[2] != 0.f;    // found_inf: no update (the grads still zeroed)
   if (skip && !ZG) return;
-  const AdamK k = {w1, b2, w2, eps, wd, amp ? amp[1] : gs, state[2], state[3]};
+  const AdamK k = {w1, b2, w2, eps, wd, amp ? amp[1] : gs, state[2], state[3],
+                   CLIP ? state[4] : 1.f};
   const int64_t n4 = n >> 2;
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -72,7 +85,7 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict_
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float mj = mm[j], vj = vv[j], vmj = vm[j];
-      w[j] = adam_elem<AMS>(w[j], gg[j], mj, vj, vmj, k);
+      w[j] = adam_elem<AMS, CLIP>(w[j], gg[j], mj, vj, vmj, k);
       mm[j] = mj;
       vv[j] = vj;
       vm[j] = vmj;
@@ -98,7 +111,7 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict_
     if constexpr (AMS) vmj = vmax[t];
     const float gj = g[t];
     if constexpr (ZG) g[t] = 0.f;
-    const float nw = adam_elem<AMS>(p[t], gj, mj, vj, vmj, k);
+    const float nw = adam_elem<AMS, CLIP>(p[t], gj, mj, vj, vmj, k);
     p[t] = nw;
     m[t] = mj;
     v[t] = vj;
@@ -108,9 +121,11 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict_
 }
 
 // sgd_kernel / sgd_amp_kernel (sgd.hip) element for element, in their arithmetic order
+template <bool CLIP>
 __device__ __forceinline__ float sgd_elem(float w, float d, float& b, float lr, float mom,
                                           float damp, float wd, int nesterov, int first,
-                                          float gs) {
+                                          float gs, float c) {
+  if constexpr (CLIP) d = clip_mul(d, c);
   d = d * gs;
   if (wd != 0.f) d += wd * w;
   if (mom != 0.f) {
@@ -120,7 +135,7 @@ __device__ __forceinline__ float sgd_elem(float w, float d, float& b, float lr, 
   return w - lr * d;
 }
 
-template <typename TS, bool ZG>
+template <typename TS, bool ZG, bool CLIP>
 __global__ __launch_bounds__(256) void sgd_dev_kernel(int64_t n, float* __restrict__ p,
                                                       float* __restrict__ g,
                                                       float* __restrict__ buf,
@@ -133,6 +148,7 @@ __global__ __launch_bounds__(256) void sgd_dev_kernel(int64_t n, float* __restri
   const bool skip = amp && amp[2] != 0.f;
   if (skip && !ZG) return;
   const float lr = state[0];
+  const float c = CLIP ? state[4] : 1.f;
   const float gs = amp ? amp[1] : gs_arg;
   const int first = amp ? (first_step && amp[4] == 0.f) : first_step;
   const bool has_buf = mom != 0.f;
@@ -152,7 +168,7 @@ __global__ __launch_bounds__(256) void sgd_dev_kernel(int64_t n, float* __restri
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float bj = bb[j];
-      w[j] = sgd_elem(w[j], gg[j], bj, lr, mom, damp, wd, nesterov, first, gs);
+      w[j] = sgd_elem<CLIP>(w[j], gg[j], bj, lr, mom, damp, wd, nesterov, first, gs, c);
       bb[j] = bj;
     }
     ((f32x4*)p)[i] = w;
@@ -173,7 +189,7 @@ __global__ __launch_bounds__(256) void sgd_dev_kernel(int64_t n, float* __restri
     float bj = (has_buf && !first) ? buf[t] : 0.f;
     const float gj = g[t];
     if constexpr (ZG) g[t] = 0.f;
-    const float nw = sgd_elem(p[t], gj, bj, lr, mom, damp, wd, nesterov, first, gs);
+    const float nw = sgd_elem<CLIP>(p[t], gj, bj, lr, mom, damp, wd, nesterov, first, gs, c);
     p[t] = nw;
     if (has_buf) buf[t] = bj;
     if (shadow) shadow[t] = from_f<TS>(nw);
@@ -203,31 +219,32 @@ extern "C" int jmt_opt_tick(float* state, double beta1, double beta2, const floa
   return JMT_OK;
 }
 
-extern "C" int jmt_adam_step(int64_t n, float* param, float* grad, float* exp_avg,
-                             float* exp_avg_sq, float* max_exp_avg_sq, const float* state,
-                             double beta1, double beta2, float eps, float weight_decay,
-                             float grad_scale, const float* amp, int zero_grad, void* shadow,
-                             int shadow_dt, void* stream) {
-  JMT_CHECK_ARG(n >= 0, "jmt_adam_step: negative n");
-  JMT_CHECK_ARG(param && grad && exp_avg && exp_avg_sq, "jmt_adam_step: null pointer");
-  JMT_CHECK_ARG(state, "jmt_adam_step: null state");
+template <bool CLIP>
+static int adam_launch(const char* fn, int64_t n, float* param, float* grad, float* exp_avg,
+                       float* exp_avg_sq, float* max_exp_avg_sq, const float* state, double beta1,
+                       double beta2, float eps, float weight_decay, float grad_scale,
+                       const float* amp, int zero_grad, void* shadow, int shadow_dt,
+                       void* stream) {
+  JMT_CHECK_ARG(n >= 0, "%s: negative n", fn);
+  JMT_CHECK_ARG(param && grad && exp_avg && exp_avg_sq, "%s: null pointer", fn);
+  JMT_CHECK_ARG(state, "%s: null state", fn);
   JMT_CHECK_ARG(al(param, 16) && al(grad, 16) && al(exp_avg, 16) && al(exp_avg_sq, 16) &&
                     al(max_exp_avg_sq, 16),
-                "jmt_adam_step: param, grad and the moment buffers must be 16-B aligned");
+                "%s: param, grad and the moment buffers must be 16-B aligned", fn);
   JMT_CHECK_ARG(!shadow || shadow_dt == JMT_BF16 || shadow_dt == JMT_F16,
-                "jmt_adam_step: shadow_dt must be bf16 or f16");
-  JMT_CHECK_ARG(al(shadow, 8), "jmt_adam_step: shadow must be 8-B aligned");
+                "%s: shadow_dt must be bf16 or f16", fn);
+  JMT_CHECK_ARG(al(shadow, 8), "%s: shadow must be 8-B aligned", fn);
   JMT_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
-                "jmt_adam_step: betas must be in [0, 1)");
+                "%s: betas must be in [0, 1)", fn);
   if (n == 0) return JMT_OK;
   const int blocks = stream_blocks(n);
   hipStream_t st = as_stream(stream);
   // torch forms 1 - beta in Python doubles and rounds once
   const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
 #define JMT_ADAM(TS, AMS, ZG)                                                                    \
-  hipLaunchKernelGGL((adam_kernel<TS, AMS, ZG>), dim3(blocks), dim3(256), 0, st, n, param, grad,  \
-                     exp_avg, exp_avg_sq, max_exp_avg_sq, state, w1, b2, w2, eps, weight_decay,   \
-                     grad_scale, amp, (TS*)shadow)
+  hipLaunchKernelGGL((adam_kernel<TS, AMS, ZG, CLIP>), dim3(blocks), dim3(256), 0, st, n, param, \
+                     grad, exp_avg, exp_avg_sq, max_exp_avg_sq, state, w1, b2, w2, eps,          \
+                     weight_decay, grad_scale, amp, (TS*)shadow)
 #define JMT_ADAM_T(TS)                                        \
   do {                                                        \
     if (max_exp_avg_sq && zero_grad) JMT_ADAM(TS, true, true); \
@@ -239,7 +256,59 @@ extern "C" int jmt_adam_step(int64_t n, float* param, float* grad, float* exp_av
   else JMT_ADAM_T(__bf16);
 #undef JMT_ADAM_T
 #undef JMT_ADAM
-  JMT_LAUNCH_CHECK("jmt_adam_step");
+  JMT_LAUNCH_CHECK(fn);
+  return JMT_OK;
+}
+
+extern "C" int jmt_adam_step(int64_t n, float* param, float* grad, float* exp_avg,
+                             float* exp_avg_sq, float* max_exp_avg_sq, const float* state,
+                             double beta1, double beta2, float eps, float weight_decay,
+                             float grad_scale, const float* amp, int zero_grad, void* shadow,
+                             int shadow_dt, void* stream) {
+  return adam_launch<false>("jmt_adam_step", n, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq,
+                            state, beta1, beta2, eps, weight_decay, grad_scale, amp, zero_grad,
+                            shadow, shadow_dt, stream);
+}
+
+extern "C" int jmt_adam_step_clip(int64_t n, float* param, float* grad, float* exp_avg,
+                                  float* exp_avg_sq, float* max_exp_avg_sq, const float* state,
+                                  double beta1, double beta2, float eps, float weight_decay,
+                                  float grad_scale, const float* amp, int zero_grad,
+                                  void* shadow, int shadow_dt, void* stream) {
+  return adam_launch<true>("jmt_adam_step_clip", n, param, grad, exp_avg, exp_avg_sq,
+                           max_exp_avg_sq, state, beta1, beta2, eps, weight_decay, grad_scale,
+                           amp, zero_grad, shadow, shadow_dt, stream);
+}
+
+template <bool CLIP>
+static int sgd_dev_launch(const char* fn, int64_t n, float* param, float* grad,
+                          float* momentum_buf, const float* state, float momentum,
+                          float dampening, float weight_decay, int nesterov, int first_step,
+                          float grad_scale, const float* amp, int zero_grad, void* shadow,
+                          int shadow_dt, void* stream) {
+  JMT_CHECK_ARG(n >= 0, "%s: negative n", fn);
+  JMT_CHECK_ARG(param && grad, "%s: null pointer", fn);
+  JMT_CHECK_ARG(state, "%s: null state", fn);
+  JMT_CHECK_ARG(momentum == 0.f || momentum_buf, "%s: momentum needs a buffer", fn);
+  JMT_CHECK_ARG(al(param, 16) && al(grad, 16) && al(momentum_buf, 16),
+                "%s: param, grad and the momentum buffer must be 16-B aligned", fn);
+  JMT_CHECK_ARG(!shadow || shadow_dt == JMT_BF16 || shadow_dt == JMT_F16,
+                "%s: shadow_dt must be bf16 or f16", fn);
+  JMT_CHECK_ARG(al(shadow, 8), "%s: shadow must be 8-B aligned", fn);
+  if (n == 0) return JMT_OK;
+  const int blocks = stream_blocks(n);
+  hipStream_t st = as_stream(stream);
+#define JMT_SGDD(TS, ZG)                                                                        \
+  hipLaunchKernelGGL((sgd_dev_kernel<TS, ZG, CLIP>), dim3(blocks), dim3(256), 0, st, n, param,   \
+                     grad, momentum_buf, state, momentum, dampening, weight_decay, nesterov,     \
+                     first_step, grad_scale, amp, (TS*)shadow)
+  const bool f16 = shadow && shadow_dt == JMT_F16;
+  if (f16 && zero_grad) JMT_SGDD(_Float16, true);
+  else if (f16) JMT_SGDD(_Float16, false);
+  else if (zero_grad) JMT_SGDD(__bf16, true);
+  else JMT_SGDD(__bf16, false);
+#undef JMT_SGDD
+  JMT_LAUNCH_CHECK(fn);
   return JMT_OK;
 }
 
@@ -248,28 +317,17 @@ extern "C" int jmt_sgd_step_dev(int64_t n, float* param, float* grad, float* mom
                                 float weight_decay, int nesterov, int first_step,
                                 float grad_scale, const float* amp, int zero_grad, void* shadow,
                                 int shadow_dt, void* stream) {
-  JMT_CHECK_ARG(n >= 0, "jmt_sgd_step_dev: negative n");
-  JMT_CHECK_ARG(param && grad, "jmt_sgd_step_dev: null pointer");
-  JMT_CHECK_ARG(state, "jmt_sgd_step_dev: null state");
-  JMT_CHECK_ARG(momentum == 0.f || momentum_buf, "jmt_sgd_step_dev: momentum needs a buffer");
-  JMT_CHECK_ARG(al(param, 16) && al(grad, 16) && al(momentum_buf, 16),
-                "jmt_sgd_step_dev: param, grad and the momentum buffer must be 16-B aligned");
-  JMT_CHECK_ARG(!shadow || shadow_dt == JMT_BF16 || shadow_dt == JMT_F16,
-                "jmt_sgd_step_dev: shadow_dt must be bf16 or f16");
-  JMT_CHECK_ARG(al(shadow, 8), "jmt_sgd_step_dev: shadow must be 8-B aligned");
-  if (n == 0) return JMT_OK;
-  const int blocks = stream_blocks(n);
-  hipStream_t st = as_stream(stream);
-#define JMT_SGDD(TS, ZG)                                                                        \
-  hipLaunchKernelGGL((sgd_dev_kernel<TS, ZG>), dim3(blocks), dim3(256), 0, st, n, param, grad,   \
-                     momentum_buf, state, momentum, dampening, weight_decay, nesterov,           \
-                     first_step, grad_scale, amp, (TS*)shadow)
-  const bool f16 = shadow && shadow_dt == JMT_F16;
-  if (f16 && zero_grad) JMT_SGDD(_Float16, true);
-  else if (f16) JMT_SGDD(_Float16, false);
-  else if (zero_grad) JMT_SGDD(__bf16, true);
-  else JMT_SGDD(__bf16, false);
-#undef JMT_SGDD
-  JMT_LAUNCH_CHECK("jmt_sgd_step_dev");
-  return JMT_OK;
+  return sgd_dev_launch<false>("jmt_sgd_step_dev", n, param, grad, momentum_buf, state, momentum,
+                               dampening, weight_decay, nesterov, first_step, grad_scale, amp,
+                               zero_grad, shadow, shadow_dt, stream);
+}
+
+extern "C" int jmt_sgd_step_dev_clip(int64_t n, float* param, float* grad, float* momentum_buf,
+                                     const float* state, float momentum, float dampening,
+                                     float weight_decay, int nesterov, int first_step,
+                                     float grad_scale, const float* amp, int zero_grad,
+                                     void* shadow, int shadow_dt, void* stream) {
+  return sgd_dev_launch<true>("jmt_sgd_step_dev_clip", n, param, grad, momentum_buf, state,
+                              momentum, dampening, weight_decay, nesterov, first_step,
+                              grad_scale, amp, zero_grad, shadow, shadow_dt, stream);
 }

@@ -244,6 +244,15 @@ _PROTOS = {
                               c_f, c_f, c_f, c_vp, c_int, c_vp, c_int, c_vp]),
     "jmt_sgd_step_dev": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_int, c_int, c_f,
                                  c_vp, c_int, c_vp, c_int, c_vp]),
+    # gradient-norm clipping (csrc/grad_norm.hip): state[4..6] = coefficient, norm, max_norm;
+    # (n, grad, state, scratch, scratch_bytes, seg_off, nseg, seg_norm, grad_scale, amp, stream)
+    "jmt_grad_norm_scratch": (c_i64, [c_i64, c_int]),
+    "jmt_grad_norm": (c_int, [c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_f, c_vp,
+                              c_vp]),
+    "jmt_adam_step_clip": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_double,
+                                   C.c_double, c_f, c_f, c_f, c_vp, c_int, c_vp, c_int, c_vp]),
+    "jmt_sgd_step_dev_clip": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_int, c_int,
+                                      c_f, c_vp, c_int, c_vp, c_int, c_vp]),
 }
 
 EXPORTED = tuple(_PROTOS)

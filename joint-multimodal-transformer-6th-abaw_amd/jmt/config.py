@@ -166,8 +166,14 @@ def optimizer(cfg: dict, params, **kw):
     """(optimizer, scheduler or None) as instantiator.get_optimizer_for_params builds them:
     FusedSGD with the lr on the device (so the schedule reaches a captured step) or FusedAdam by
     `opt__name_optimizer`, the scheduler by `opt__lr_scheduler` / `opt__name_lr_scheduler`.  kw
-    goes to the optimizer (shadow_dtype, fuse_zero_grad)."""
+    goes to the optimizer (shadow_dtype, fuse_zero_grad, max_grad_norm).  An optional
+    `opt__clip_grad_norm` (not in the reference's file) turns gradient-norm clipping on at that
+    threshold; absent or <= 0 is off, and an explicit max_grad_norm keyword wins."""
     from . import optim
+    if "max_grad_norm" not in kw:
+        clip = cfg["model_params"].get("opt__clip_grad_norm")
+        if clip is not None and float(clip) > 0:
+            kw["max_grad_norm"] = float(clip)
     name = str(cfg["model_params"].get("opt__name_optimizer", "sgd")).lower()
     if name == "sgd":
         opt = optim.FusedSGD(params, device_lr=True, **sgd_kwargs(cfg), **kw)

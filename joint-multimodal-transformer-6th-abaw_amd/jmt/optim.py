@@ -10,6 +10,7 @@ Parameters that never receive a gradient (the reference's unused `final_encoder`
 so `used_parameters()` finds them with one probe backward."""
 from __future__ import annotations
 
+import math
 import os
 from typing import Iterable, List, Optional, Tuple
 
@@ -25,9 +26,20 @@ def _bump_grad_gen(_p):
 
 
 def _state_block(lr: float, dev) -> torch.Tensor:
-    """The device optimizer state of include/jmt.h: fp32[8] = lr, step, step_size, bc2_sqrt, 4
-    reserved."""
+    """The device optimizer state of include/jmt.h: fp32[8] = lr, step, step_size, bc2_sqrt,
+    clip coefficient, gradient norm, max_norm, 1 reserved."""
     return torch.tensor([lr, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+
+
+def _check_max_grad_norm(kind: str, max_grad_norm) -> Optional[float]:
+    """None (no clipping), or the threshold as a float: > 0, float("inf") allowed (measure only)."""
+    if max_grad_norm is None:
+        return None
+    x = float(max_grad_norm)
+    if math.isnan(x) or x <= 0.0:
+        raise ValueError(f"{kind}: max_grad_norm must be > 0 (float('inf') measures without "
+                         f"clipping) or None, not {max_grad_norm!r}")
+    return x
 
 
 class _FlatOptimizer:
@@ -47,9 +59,20 @@ class _FlatOptimizer:
     (p.grad.add_/copy_ by hand, a helper writing into the flat views) is invisible to it and the
     next backward would add onto the stale values: call zero_grad(force=True) after such a
     write, or set JMT_CHECK_ZERO_GRAD=1 to have every skipped fill verify (one reduction + host
-    sync) that the gradients are in fact zero."""
+    sync) that the gradients are in fact zero.
+
+    max_grad_norm (FusedSGD(device_lr=True), FusedAdam): torch.nn.utils.clip_grad_norm_ (L2)
+    folded into the step.  jmt_grad_norm (a read-only pass over the gradient buffer and a
+    one-block fold, no floating-point atomics: bitwise reproducible) leaves the norm of the
+    unscaled gradient, the coefficient min(1, max_norm / (norm + 1e-6)) and the per-parameter
+    norms on the device, and the step kernel multiplies every gradient by the coefficient as it
+    reads it (the *_clip entry points).  Nothing is read on the host and the step still captures
+    into a hipGraph; set_max_grad_norm() is legal between replays, grad_norm() / clip_coef() /
+    grad_norms() return device tensors.  None launches nothing and steps through the entry points
+    without clipping."""
 
     state: Optional[torch.Tensor] = None
+    max_grad_norm: Optional[float] = None
     _BUFFERS: tuple = ()          # names of the per-element state buffers (state_dict)
 
     def _init_flat(self, params: Iterable[torch.nn.Parameter], lr: float,
@@ -138,11 +161,72 @@ class _FlatOptimizer:
         """The learning rate last set (the host's copy: nothing is read from the device)."""
         return self.lr
 
+    # ---------------------------------------------------------------- gradient-norm clipping
+    def _init_clip(self, max_grad_norm: Optional[float]):
+        """After the state block exists.  The segment table is the parameters' offsets: segment
+        i = parameter i and the zero padding behind it."""
+        self.max_grad_norm = max_grad_norm
+        if max_grad_norm is None:
+            return
+        dev = self.flat_p.device
+        self.state[6:7].fill_(max_grad_norm)
+        self._seg_off = torch.tensor(self.offsets + [self.numel], dtype=torch.int64, device=dev)
+        self._seg_norm = torch.zeros(len(self.params), dtype=torch.float32, device=dev)
+        nbytes = int(_lib.load().jmt_grad_norm_scratch(self.numel, len(self.params)))
+        if nbytes < 0:
+            raise _lib.JMTError(f"jmt_grad_norm_scratch refuses {self.numel} elements in "
+                                f"{len(self.params)} segments")
+        self._norm_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+
+    def _grad_norm(self, grad_scale: float, amp_state: Optional[torch.Tensor]):
+        """The norm launches of a clipped step: state[4] / state[5] and the per-parameter norms."""
+        launch = lambda: _lib.call(
+            "jmt_grad_norm", self.numel, self.flat_g.data_ptr(), self.state.data_ptr(),
+            self._norm_scratch.data_ptr(), self._norm_scratch.numel() * 8,
+            self._seg_off.data_ptr(), len(self.params), self._seg_norm.data_ptr(), grad_scale,
+            self._ptr(amp_state), ops.stream())
+        ops._hooked({"family": "grad_norm", "flops": 0.0, "bytes": 4.0 * self.numel}, launch)
+
+    def _clipping(self) -> None:
+        if self.max_grad_norm is None:
+            raise RuntimeError(f"{type(self).__name__}: built without max_grad_norm (pass "
+                               "float('inf') to measure the norm without clipping)")
+
+    def set_max_grad_norm(self, max_grad_norm: float):
+        """Set the clipping threshold: a stream-ordered fill of state[6], as set_lr is for
+        state[0] (no host synchronisation, legal between replays of a captured step)."""
+        self._clipping()
+        self.max_grad_norm = _check_max_grad_norm(type(self).__name__, float(max_grad_norm))
+        self.state[6:7].fill_(self.max_grad_norm)
+
+    def grad_norm(self) -> torch.Tensor:
+        """The last step's L2 norm of the unscaled gradient before clipping: a 0-dim view of the
+        device state block (no synchronisation; read it when it is needed, e.g. once per epoch)."""
+        self._clipping()
+        return self.state[5]
+
+    def clip_coef(self) -> torch.Tensor:
+        """The last step's coefficient min(1, max_norm / (norm + 1e-6)), a 0-dim device view."""
+        self._clipping()
+        return self.state[4]
+
+    def grad_norms(self) -> torch.Tensor:
+        """The last step's per-parameter norms of the unscaled gradient, (len(params),) fp32 on
+        the device, in `params` order."""
+        self._clipping()
+        return self._seg_norm
+
     def _ptr(self, t: Optional[torch.Tensor]):
         return t.data_ptr() if t is not None else None
 
     def _shadow_dt(self) -> int:
         return ops.dt(self.shadow) if self.shadow is not None else _lib.BF16
+
+    def _step_bytes(self, arrays: int) -> float:
+        """A step launch's traffic for the launch hook: `arrays` fp32 buffers read and written
+        (the gradient written only with fuse_zero_grad) and the shadow written."""
+        rw = 2 * arrays - (0 if self.fuse_zero_grad else 1)
+        return float(self.numel) * (4 * rw + (2 if self.shadow is not None else 0))
 
     # ---------------------------------------------------------------- resume
     def _host_state(self) -> dict:
@@ -178,6 +262,8 @@ class _FlatOptimizer:
                                  "present on one side only")
             if mine is not None:
                 mine.copy_(theirs)
+        if self.max_grad_norm is not None:        # this optimizer's threshold, not the file's
+            self.state[6:7].fill_(self.max_grad_norm)
         self.flat_p.copy_(sd["flat_p"])
         if self.shadow is not None:
             ops.cast(self.flat_p, self.shadow.dtype, out=self.shadow)
@@ -191,18 +277,24 @@ class FusedSGD(_FlatOptimizer):
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, momentum: float = 0.0,
                  dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
                  shadow_dtype: Optional[torch.dtype] = None, fuse_zero_grad: bool = False,
-                 device_lr: bool = False):
-        """fuse_zero_grad: see _FlatOptimizer (jmt_sgd_step_zero).
+                 device_lr: bool = False, max_grad_norm: Optional[float] = None):
+        """fuse_zero_grad, max_grad_norm: see _FlatOptimizer (jmt_sgd_step_zero; clipping needs
+        device_lr=True, the coefficient lives in the device state block).
 
         device_lr: the learning rate lives in the device state block and the step goes through
         jmt_sgd_step_dev, so set_lr() (an lr scheduler) takes effect inside a captured graph.
         Off by default: the lr is then a kernel argument, fixed at capture."""
+        max_grad_norm = _check_max_grad_norm("FusedSGD", max_grad_norm)
+        if max_grad_norm is not None and not device_lr:
+            raise ValueError("FusedSGD: max_grad_norm needs device_lr=True (the clip coefficient "
+                             "is read from the device state block)")
         self._init_flat(params, lr, shadow_dtype, fuse_zero_grad)
         self.momentum, self.dampening = momentum, dampening
         self.weight_decay, self.nesterov = weight_decay, nesterov
         dev = self.flat_p.device
         self.buf = torch.zeros(self.numel, dtype=torch.float32, device=dev) if momentum else None
         self.state = _state_block(lr, dev) if device_lr else None
+        self._init_clip(max_grad_norm)
         self.first = True
 
     def _host_state(self) -> dict:
@@ -213,11 +305,16 @@ class FusedSGD(_FlatOptimizer):
         self._amp = bool(sd["amp"])
 
     def _step_dev(self, grad_scale: float, amp_state: Optional[torch.Tensor]):
-        _lib.call("jmt_sgd_step_dev", self.numel, self.flat_p.data_ptr(), self.flat_g.data_ptr(),
-                  self._ptr(self.buf), self.state.data_ptr(), self.momentum, self.dampening,
-                  self.weight_decay, int(self.nesterov), int(self.first), grad_scale,
-                  self._ptr(amp_state), int(self.fuse_zero_grad), self._ptr(self.shadow),
-                  self._shadow_dt(), ops.stream())
+        clip = self.max_grad_norm is not None
+        if clip:
+            self._grad_norm(grad_scale, amp_state)
+        fn = "jmt_sgd_step_dev_clip" if clip else "jmt_sgd_step_dev"
+        launch = lambda: _lib.call(
+            fn, self.numel, self.flat_p.data_ptr(), self.flat_g.data_ptr(), self._ptr(self.buf),
+            self.state.data_ptr(), self.momentum, self.dampening, self.weight_decay,
+            int(self.nesterov), int(self.first), grad_scale, self._ptr(amp_state),
+            int(self.fuse_zero_grad), self._ptr(self.shadow), self._shadow_dt(), ops.stream())
+        ops._hooked({"family": fn[4:], "flops": 0.0, "bytes": self._step_bytes(3)}, launch)
 
     @torch.no_grad()
     def step_amp(self, amp_state: torch.Tensor):
@@ -264,9 +361,11 @@ class FusedAdam(_FlatOptimizer):
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, amsgrad: bool = False,
-                 shadow_dtype: Optional[torch.dtype] = None, fuse_zero_grad: bool = False):
+                 shadow_dtype: Optional[torch.dtype] = None, fuse_zero_grad: bool = False,
+                 max_grad_norm: Optional[float] = None):
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"FusedAdam: betas {betas} must be in [0, 1)")
+        max_grad_norm = _check_max_grad_norm("FusedAdam", max_grad_norm)
         self._init_flat(params, lr, shadow_dtype, fuse_zero_grad)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), eps
         self.weight_decay, self.amsgrad = weight_decay, bool(amsgrad)
@@ -276,15 +375,23 @@ class FusedAdam(_FlatOptimizer):
         self.max_exp_avg_sq = (torch.zeros(self.numel, dtype=torch.float32, device=dev)
                                if self.amsgrad else None)
         self.state = _state_block(lr, dev)
+        self._init_clip(max_grad_norm)
 
     def _step(self, grad_scale: float, amp_state: Optional[torch.Tensor]):
         st, amp, s = self.state.data_ptr(), self._ptr(amp_state), ops.stream()
-        _lib.call("jmt_opt_tick", st, self.betas[0], self.betas[1], amp, s)
-        _lib.call("jmt_adam_step", self.numel, self.flat_p.data_ptr(), self.flat_g.data_ptr(),
-                  self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                  self._ptr(self.max_exp_avg_sq), st, self.betas[0], self.betas[1], self.eps,
-                  self.weight_decay, grad_scale, amp, int(self.fuse_zero_grad),
-                  self._ptr(self.shadow), self._shadow_dt(), s)
+        clip = self.max_grad_norm is not None
+        ops._hooked({"family": "opt_tick", "flops": 0.0, "bytes": 32.0}, lambda: _lib.call(
+            "jmt_opt_tick", st, self.betas[0], self.betas[1], amp, s))
+        if clip:
+            self._grad_norm(grad_scale, amp_state)
+        fn = "jmt_adam_step_clip" if clip else "jmt_adam_step"
+        launch = lambda: _lib.call(
+            fn, self.numel, self.flat_p.data_ptr(), self.flat_g.data_ptr(),
+            self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self._ptr(self.max_exp_avg_sq),
+            st, self.betas[0], self.betas[1], self.eps, self.weight_decay, grad_scale, amp,
+            int(self.fuse_zero_grad), self._ptr(self.shadow), self._shadow_dt(), s)
+        ops._hooked({"family": fn[4:], "flops": 0.0,
+                     "bytes": self._step_bytes(5 if self.amsgrad else 4)}, launch)
         self._clean_gen = F._grad_gen[0]
 
     @torch.no_grad()
