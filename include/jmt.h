@@ -571,6 +571,32 @@ int jmt_head_bwd_drop(int h_dt, int gy_dt, int64_t rows, int hid, int k, const v
 int jmt_dropout_reference(const uint32_t ctr[4], int64_t rows, int64_t cols, int64_t split,
                           float p0, float p1, float* out);
 
+/* The head entries with a row map on y / gy (same ABI number: entry points added, none changed).
+ * Memory row r of h (and of dh) pairs with row (r mod P) * Q + r div P of y_g / gy_g; P >= 1,
+ * Q >= 1, P * Q = rows < 2^31, anything else is JMT_ERR_ARG.  P = rows, Q = 1 is the identity.
+ * With h in (B, T) row order, P = T and Q = B make y a contiguous (T, B, k) tensor and read gy
+ * from one: the seq-first predictions need no transposing copy.  The dropout counter of the
+ * *_perm_drop entries stays the memory row r of h.  Per output element the arithmetic and the
+ * order of every sum are those of the entries above. */
+int jmt_head_fwd_perm(int h_dt, int y_dt, int64_t rows, int hid, int k, const void* h,
+                      int64_t ldh, const void* w2_0, const void* w2_1, const float* b2_0,
+                      const float* b2_1, void* y_0, void* y_1, int64_t ldy, int64_t P, int64_t Q,
+                      void* stream);
+int jmt_head_bwd_perm(int h_dt, int gy_dt, int64_t rows, int hid, int k, const void* h,
+                      int64_t ldh, const void* w2_0, const void* w2_1, const void* gy_0,
+                      const void* gy_1, int64_t ldgy, void* dh, int64_t lddh, float* dw2_0,
+                      float* dw2_1, float* db2_0, float* db2_1, float* partials, int64_t P,
+                      int64_t Q, void* stream);
+int jmt_head_fwd_perm_drop(int h_dt, int y_dt, int64_t rows, int hid, int k, const void* h,
+                           int64_t ldh, const void* w2_0, const void* w2_1, const float* b2_0,
+                           const float* b2_1, void* y_0, void* y_1, int64_t ldy, int64_t P,
+                           int64_t Q, float p0, float p1, const uint32_t* ctr, void* stream);
+int jmt_head_bwd_perm_drop(int h_dt, int gy_dt, int64_t rows, int hid, int k, const void* h,
+                           int64_t ldh, const void* w2_0, const void* w2_1, const void* gy_0,
+                           const void* gy_1, int64_t ldgy, void* dh, int64_t lddh, float* dw2_0,
+                           float* dw2_1, float* db2_0, float* db2_1, float* partials, int64_t P,
+                           int64_t Q, float p0, float p1, const uint32_t* ctr, void* stream);
+
 /* ------------------------------------------------------------------ CCC losses
  * kind 0: losses/loss.py:8-32 CCCLoss (digitize_num k; k>1: pred is (n,k) logits, softmax over
  *         bins = linspace(range) first)
@@ -595,6 +621,16 @@ int jmt_ccc_finish_add(int kind, int world, const double* stats_all, int64_t bs,
 int jmt_ccc_bwd(int kind, int pred_dt, int64_t n, int k, const void* pred, const float* label,
                 float ignore, float lo, float hi, const double* coef, const float* grad_loss,
                 void* dpred, void* stream);
+/* One rank (same ABI number: entry points added): jmt_ccc_stats followed by
+ * jmt_ccc_finish(_add)(world = 1) on those statistics, in one launch — the statistics block's
+ * first thread runs the finish.  Writes stats, loss and coef exactly as the two calls do. */
+int jmt_ccc_stats_finish(int kind, int pred_dt, int64_t n, int k, const void* pred,
+                         const float* label, float ignore, float lo, float hi, double* stats,
+                         int64_t bs, float eps, float* loss, double* coef, void* stream);
+int jmt_ccc_stats_finish_add(int kind, int pred_dt, int64_t n, int k, const void* pred,
+                             const float* label, float ignore, float lo, float hi, double* stats,
+                             int64_t bs, float eps, const float* add, float* loss, double* coef,
+                             void* stream);
 /* CELoss (losses/loss.py:34-51; replaces its host numpy digitize + F.cross_entropy): labels
  * digitized on the device into k bins (np.digitize over linspace(lo, hi, k + 1) - 1, top bin
  * clamped), x (n, k) logits, optional class weights (k floats, NULL = none).

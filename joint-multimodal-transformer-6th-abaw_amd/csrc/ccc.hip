@@ -62,11 +62,11 @@ __device__ __forceinline__ void block_sum3_d(double& a, double& b, double& c, do
 // registers from pass 1 (all their loads issued together), so for n <= RC * CT (the JMT batches:
 // B*T = 19,200) pass 2 reads no memory; beyond that the rest is re-read.
 constexpr int RC = 24;
+// (the body of ccc_stats_kernel and of ccc_stats_finish_kernel; `red`: 3 * (CT / 64) doubles of LDS)
 template <typename T>
-__global__ __launch_bounds__(CT) void ccc_stats_kernel(int kind, int64_t n, int k, const T* pred,
-                                                       const float* label, float ignore, float lo,
-                                                       float hi, double* stats) {
-  __shared__ double red[3 * (CT / 64)];
+__device__ __forceinline__ void ccc_stats_block(int kind, int64_t n, int k, const T* pred,
+                                                const float* label, float ignore, float lo,
+                                                float hi, double* stats, double* red) {
   float xs[RC], ys[RC];
 #pragma unroll
   for (int r = 0; r < RC; ++r) {
@@ -120,6 +120,14 @@ __global__ __launch_bounds__(CT) void ccc_stats_kernel(int kind, int64_t n, int 
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(CT) void ccc_stats_kernel(int kind, int64_t n, int k, const T* pred,
+                                                       const float* label, float ignore, float lo,
+                                                       float hi, double* stats) {
+  __shared__ double red[3 * (CT / 64)];
+  ccc_stats_block(kind, n, k, pred, label, ignore, lo, hi, stats, red);
+}
+
 // Combine rank statistics in fixed rank order, then loss + gradient coefficients.
 //   coef = {c0, c1, c2, mean_x, mean_y, valid, 0, 0};  dL/dx_i = c0 + c1 (x_i - mx) + c2 (y_i - my)
 // bs (kind 1, CCCLoss.py:17 `y_pred.size(0)` before masking): bs >= 1 is used as given (the
@@ -127,9 +135,12 @@ __global__ __launch_bounds__(CT) void ccc_stats_kernel(int kind, int64_t n, int 
 // means "1-D predictions": size(0) of the GATHERED batch = the sum of the ranks' pre-mask counts.
 // `add` (may be NULL): the loss written is *add + this loss, rounded once as torch's fp32
 // `l1 + l2` of train.py:311 (the two criteria of a step summed without a separate add kernel)
-__global__ void ccc_finish_kernel(int kind, int world, const double* st, int64_t bs_in, float eps,
-                                  const float* add, float* loss, double* coef) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// One thread's work, shared by ccc_finish_kernel and ccc_stats_finish_kernel.  Not inlined: both
+// kernels run the one compiled body, so the fused launch cannot round differently from the
+// two-kernel path (contraction is decided once).
+__device__ __noinline__ void ccc_finish_one(int kind, int world, const double* st, int64_t bs_in,
+                                            float eps, const float* add, float* loss,
+                                            double* coef) {
   auto put = [&](float v) { *loss = add ? *add + v : v; };
   double n = st[0], mx = st[1], my = st[2], Sxx = st[3], Syy = st[4], Sxy = st[5];
   double bsd = (double)bs_in;
@@ -204,6 +215,27 @@ __global__ void ccc_finish_kernel(int kind, int world, const double* st, int64_t
     coef[2] = -dccc_dSxy;
     coef[5] = 1.0;
   }
+}
+
+__global__ void ccc_finish_kernel(int kind, int world, const double* st, int64_t bs_in, float eps,
+                                  const float* add, float* loss, double* coef) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  ccc_finish_one(kind, world, st, bs_in, eps, add, loss, coef);
+}
+
+// One rank: the statistics block, then thread 0 finishes from the statistics it has just written
+// (its own stores: no fence needed) — ccc_stats_kernel + ccc_finish_kernel(world = 1) in one
+// launch.  `stats` is still written, as the two-kernel path leaves it.
+template <typename T>
+__global__ __launch_bounds__(CT) void ccc_stats_finish_kernel(int kind, int64_t n, int k,
+                                                              const T* pred, const float* label,
+                                                              float ignore, float lo, float hi,
+                                                              double* stats, int64_t bs_in,
+                                                              float eps, const float* add,
+                                                              float* loss, double* coef) {
+  __shared__ double red[3 * (CT / 64)];
+  ccc_stats_block(kind, n, k, pred, label, ignore, lo, hi, stats, red);
+  if (threadIdx.x == 0) ccc_finish_one(kind, 1, stats, bs_in, eps, add, loss, coef);
 }
 
 template <typename T>
@@ -469,6 +501,38 @@ extern "C" int jmt_ccc_finish_add(int kind, int world, const double* stats_all, 
   hipLaunchKernelGGL(ccc_finish_kernel, dim3(1), dim3(64), 0, as_stream(stream), kind, world,
                      stats_all, bs, eps, add, loss, coef);
   JMT_LAUNCH_CHECK("jmt_ccc_finish");
+  return JMT_OK;
+}
+
+extern "C" int jmt_ccc_stats_finish(int kind, int pred_dt, int64_t n, int k, const void* pred,
+                                    const float* label, float ignore, float lo, float hi,
+                                    double* stats, int64_t bs, float eps, float* loss,
+                                    double* coef, void* stream) {
+  return jmt_ccc_stats_finish_add(kind, pred_dt, n, k, pred, label, ignore, lo, hi, stats, bs, eps,
+                                  nullptr, loss, coef, stream);
+}
+
+extern "C" int jmt_ccc_stats_finish_add(int kind, int pred_dt, int64_t n, int k, const void* pred,
+                                        const float* label, float ignore, float lo, float hi,
+                                        double* stats, int64_t bs, float eps, const float* add,
+                                        float* loss, double* coef, void* stream) {
+  JMT_CHECK_ARG(kind == 0 || kind == 1, "jmt_ccc_stats_finish: kind");
+  JMT_CHECK_ARG(k >= 1 && k <= MAXK, "jmt_ccc_stats_finish: digitize_num %d unsupported", k);
+  JMT_CHECK_ARG(n >= 0, "jmt_ccc_stats_finish: negative n");
+  JMT_CHECK_ARG(stats && loss && coef && (n == 0 || (pred && label)),
+                "jmt_ccc_stats_finish: null pointer");
+  hipStream_t st = as_stream(stream);
+#define CSF(T)                                                                                  \
+  hipLaunchKernelGGL((ccc_stats_finish_kernel<T>), dim3(1), dim3(CT), 0, st, kind, n, k,        \
+                     (const T*)pred, label, ignore, lo, hi, stats, bs, eps, add, loss, coef)
+  switch (pred_dt) {
+    case JMT_F32: CSF(float); break;
+    case JMT_BF16: CSF(__bf16); break;
+    case JMT_F16: CSF(_Float16); break;
+    default: return set_error(JMT_ERR_ARG, "jmt_ccc_stats_finish: dtype");
+  }
+#undef CSF
+  JMT_LAUNCH_CHECK("jmt_ccc_stats_finish");
   return JMT_OK;
 }
 

@@ -23,6 +23,18 @@
 // Replaces, per step (B=64, T=300): the N = 1 forward GEMM (10 us), the K = 1 masked dgrad GEMM
 // (16 us), the M = 1 fp32 weight-gradient GEMM with its 256-way split-K (36 us) and the bias
 // column sum; HBM-bound: the kernels read h once (9.8 MB) and write dh once.
+//
+// Row loads are issued ahead: a wave loads its rows of h (and, backward, of gy) into registers in
+// batches before the shuffle / accumulate chain that consumes them, instead of one dependent load
+// per row; rows >= `rows` are predicated off (no load is issued past the last row).  Every sum
+// keeps its order, so the results are those of the row-at-a-time walk, bit for bit.
+//
+// The PERM instantiations (jmt_head_*_perm) store y and read gy through a row map: memory row r
+// of h pairs with row (r mod P) * Q + r div P of y / gy, P * Q = rows.  With h in (B, T) memory
+// order and P = T, Q = B the predictions come out as a contiguous (T, B, k) tensor — the
+// seq-first layout two_transformers.py returns — without a transposing copy after the kernel.
+#include <type_traits>
+
 #include "common.h"
 #include "dropout.h"
 
@@ -34,12 +46,12 @@ constexpr int HD_RPW = 16;         // rows per wave per block
 
 template <typename T> struct V4l;   // 4 consecutive 16-bit values <-> 8-B accesses
 template <> struct V4l<__bf16> {
-  static __device__ __forceinline__ void ld(const __bf16* p, float* v) {
-    const uint2 u = *(const uint2*)p;
+  static __device__ __forceinline__ void cvt(const uint2 u, float* v) {
     const __bf16* e = (const __bf16*)&u;
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = (float)e[i];
   }
+  static __device__ __forceinline__ void ld(const __bf16* p, float* v) { cvt(*(const uint2*)p, v); }
   static __device__ __forceinline__ void st(__bf16* p, const float* v) {
     __bf16 e[4];
 #pragma unroll
@@ -48,17 +60,47 @@ template <> struct V4l<__bf16> {
   }
 };
 template <> struct V4l<_Float16> {
-  static __device__ __forceinline__ void ld(const _Float16* p, float* v) {
-    const uint2 u = *(const uint2*)p;
+  static __device__ __forceinline__ void cvt(const uint2 u, float* v) {
     const _Float16* e = (const _Float16*)&u;
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = (float)e[i];
+  }
+  static __device__ __forceinline__ void ld(const _Float16* p, float* v) {
+    cvt(*(const uint2*)p, v);
   }
   static __device__ __forceinline__ void st(_Float16* p, const float* v) {
     _Float16 e[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) e[i] = (_Float16)v[i];
     *(uint2*)p = *(const uint2*)e;
+  }
+};
+
+// a lane's quad of row r as loaded; `in` false: no load is issued
+template <bool FULL>
+__device__ __forceinline__ uint2 ld_quad(const void* p, bool in) {
+  uint2 u = make_uint2(0u, 0u);
+  if (FULL || in) u = *(const uint2*)p;
+  return u;
+}
+
+// rows a wave loads ahead of the chain that consumes them: all 16 for k = 1 (8 B of h and one gy
+// per row and lane); the k <= 24 kernels hold k quads of weights (and, backward, of weight
+// gradient sums) per lane and batch fewer
+template <int K> struct HeadAhead {
+  static constexpr int FWD = K == 1 ? HD_RPW : 4;
+  static constexpr int BWD = K == 1 ? HD_RPW : 2;
+};
+
+// the row of y / gy that pairs with memory row r of h, walked row by row: (r mod P) * Q + r div P
+struct RowWalk {
+  uint32_t m, d, P;
+  int64_t Q;
+  __device__ __forceinline__ RowWalk(int64_t r, int64_t P_, int64_t Q_)
+      : m((uint32_t)r % (uint32_t)P_), d((uint32_t)r / (uint32_t)P_), P((uint32_t)P_), Q(Q_) {}
+  __device__ __forceinline__ int64_t row() const { return (int64_t)m * Q + d; }
+  __device__ __forceinline__ void next() {
+    if (++m == P) { m = 0; ++d; }
   }
 };
 
@@ -88,6 +130,7 @@ struct HeadArgs {
   float* db2[2];
   int64_t rows;
   int k;
+  int64_t P, Q;          // row map of y / gy (the PERM instantiations; P * Q = rows < 2^31)
 };
 
 // Dropout between the ReLU and the output layers (the DROP instantiations: jmt_head_*_drop).  A
@@ -107,7 +150,7 @@ struct HeadArgsDrop : HeadArgs {
 template <bool DROP> struct HeadParam { typedef HeadArgs t; };
 template <> struct HeadParam<true> { typedef HeadArgsDrop t; };
 
-template <typename TH, typename TY, int K, bool DROP>
+template <typename TH, typename TY, int K, bool DROP, bool PERM>
 __global__ __launch_bounds__(256) void head_fwd_kernel(typename HeadParam<DROP>::t a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = lane >> 5, c = 4 * (lane & 31);
@@ -117,7 +160,11 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(typename HeadParam<DROP>:
 #pragma unroll
   for (int o = 0; o < K; ++o)
     if (o < k) V4l<TH>::ld(W + o * HD_HID + c, wv[o]);
+  // the biases once, in registers (a load per stored element would wait on the rows in flight)
   const float* bp = a.b2[g];
+  float bv[K];
+#pragma unroll
+  for (int o = 0; o < K; ++o) bv[o] = (bp && o < k) ? bp[o] : 0.f;
   TY* yp = (TY*)a.y[g];
   uint32_t ctr[4] = {0u, 0u, 0u, 0u}, dT = 0u;
   float ds = 1.f;
@@ -128,29 +175,51 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(typename HeadParam<DROP>:
     ds = g ? a.dr.s[1] : a.dr.s[0];
   }
   const int64_t r0 = ((int64_t)blockIdx.x * 4 + w) * HD_RPW;
-  for (int i = 0; i < HD_RPW; ++i) {
-    const int64_t r = r0 + i;
-    if (r >= a.rows) break;
-    float hv[4];
-    V4l<TH>::ld((const TH*)a.h + r * a.ldh + g * HD_HID + c, hv);
-    if (DROP) {
-      float m[4];
-      dropout_quad(ctr, (uint32_t)r, (uint32_t)lane, dT, ds, m);
+  if (r0 >= a.rows) return;
+  const TH* hp = (const TH*)a.h + g * HD_HID + c;
+  constexpr int NB = HeadAhead<K>::FWD;
+  // FULL: all 16 rows of the wave exist (every load unconditional); else the last wave's walk
+  auto walk = [&](auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    RowWalk rw(PERM ? r0 : 0, PERM ? a.P : 1, PERM ? a.Q : 1);
+    for (int i0 = 0; i0 < HD_RPW; i0 += NB) {
+      if (!FULL && r0 + i0 >= a.rows) break;
+      uint2 raw[NB];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) hv[e] *= m[e];
-    }
+      for (int j = 0; j < NB; ++j) {
+        const int64_t r = r0 + i0 + j;
+        raw[j] = ld_quad<FULL>(hp + r * a.ldh, r < a.rows);
+      }
 #pragma unroll
-    for (int o = 0; o < K; ++o) {
-      if (o < k) {            // (no break: the loop must unroll to keep wv in registers)
-        float s = hv[0] * wv[o][0] + hv[1] * wv[o][1] + hv[2] * wv[o][2] + hv[3] * wv[o][3];
-        s = half_sum(s);
-        if ((lane & 31) == 0) yp[r * a.ldy + o] = from_f<TY>(s + (bp ? bp[o] : 0.f));
+      for (int j = 0; j < NB; ++j) {
+        const int64_t r = r0 + i0 + j;
+        if (!FULL && r >= a.rows) continue;   // (no break: raw[] must stay in registers)
+        const int64_t yr = PERM ? rw.row() : r;
+        if (PERM) rw.next();
+        float hv[4];
+        V4l<TH>::cvt(raw[j], hv);
+        if (DROP) {
+          float m[4];
+          dropout_quad(ctr, (uint32_t)r, (uint32_t)lane, dT, ds, m);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) hv[e] *= m[e];
+        }
+#pragma unroll
+        for (int o = 0; o < K; ++o) {
+          if (o < k) {            // (no break: the loop must unroll to keep wv in registers)
+            float s = hv[0] * wv[o][0] + hv[1] * wv[o][1] + hv[2] * wv[o][2] + hv[3] * wv[o][3];
+            s = half_sum(s);
+            if ((lane & 31) == 0) yp[yr * a.ldy + o] = from_f<TY>(s + bv[o]);
+          }
+        }
       }
     }
-  }
+  };
+  if (r0 + HD_RPW <= a.rows) walk(std::true_type{});
+  else walk(std::false_type{});
 }
 
-template <typename TH, typename TG, int K, bool DROP>
+template <typename TH, typename TG, int K, bool DROP, bool PERM>
 __global__ __launch_bounds__(256) void head_bwd_kernel(typename HeadParam<DROP>::t a) {
   __shared__ float red[2][HD_KMAX * HD_HID + HD_KMAX];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -175,33 +244,61 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(typename HeadParam<DROP>:
     ds = g ? a.dr.s[1] : a.dr.s[0];
   }
   const int64_t r0 = ((int64_t)blockIdx.x * 4 + w) * HD_RPW;
-  for (int i = 0; i < HD_RPW; ++i) {
-    const int64_t r = r0 + i;
-    if (r >= a.rows) break;
-    float hv[4], d[4] = {0.f, 0.f, 0.f, 0.f};
-    V4l<TH>::ld((const TH*)a.h + r * a.ldh + g * HD_HID + c, hv);
-    if (DROP) {
-      float m[4];
-      dropout_quad(ctr, (uint32_t)r, (uint32_t)lane, dT, ds, m);
+  const TH* hp = (const TH*)a.h + g * HD_HID + c;
+  constexpr int NB = HeadAhead<K>::BWD;
+  // (a wave past the last row walks nothing and adds its zero sums to the block's, as before)
+  auto walk = [&](auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    RowWalk rw(PERM ? r0 : 0, PERM ? a.P : 1, PERM ? a.Q : 1);
+    for (int i0 = 0; i0 < HD_RPW; i0 += NB) {
+      if (!FULL && r0 + i0 >= a.rows) break;
+      uint2 raw[NB];
+      TG gq[NB][K];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) hv[e] *= m[e];
-    }
+      for (int j = 0; j < NB; ++j) {
+        const int64_t r = r0 + i0 + j;
+        const bool in = r < a.rows;
+        raw[j] = ld_quad<FULL>(hp + r * a.ldh, in);
+        const int64_t yr = PERM ? rw.row() : r;
+        if (PERM) rw.next();
 #pragma unroll
-    for (int o = 0; o < K; ++o) {
-      if (o < k) {
-        const float gy = to_f(gp[r * a.ldgy + o]);
-        ab[o] += gy;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          d[e] += gy * wv[o][e];
-          aw[o][e] += gy * hv[e];
+        for (int o = 0; o < K; ++o) {
+          gq[j][o] = from_f<TG>(0.f);
+          if (o < k && (FULL || in)) gq[j][o] = gp[yr * a.ldgy + o];
         }
       }
-    }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) d[e] = hv[e] > 0.f ? (DROP ? ds * d[e] : d[e]) : 0.f;
-    V4l<TH>::st((TH*)a.dh + r * a.lddh + g * HD_HID + c, d);
-  }
+      for (int j = 0; j < NB; ++j) {
+        const int64_t r = r0 + i0 + j;
+        if (!FULL && r >= a.rows) continue;   // (no break: raw[] / gq[] must stay in registers)
+        float hv[4], d[4] = {0.f, 0.f, 0.f, 0.f};
+        V4l<TH>::cvt(raw[j], hv);
+        if (DROP) {
+          float m[4];
+          dropout_quad(ctr, (uint32_t)r, (uint32_t)lane, dT, ds, m);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) hv[e] *= m[e];
+        }
+#pragma unroll
+        for (int o = 0; o < K; ++o) {
+          if (o < k) {
+            const float gy = to_f(gq[j][o]);
+            ab[o] += gy;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              d[e] += gy * wv[o][e];
+              aw[o][e] += gy * hv[e];
+            }
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = hv[e] > 0.f ? (DROP ? ds * d[e] : d[e]) : 0.f;
+        V4l<TH>::st((TH*)a.dh + r * a.lddh + g * HD_HID + c, d);
+      }
+    }
+  };
+  if (r0 + HD_RPW <= a.rows) walk(std::true_type{});
+  else if (r0 < a.rows) walk(std::false_type{});
   // block sum of the weight / bias gradient partials, waves added in a fixed order
   for (int ww = 0; ww < 4; ++ww) {
     if (w == ww) {
@@ -286,10 +383,22 @@ static int head_drop_args(const char* name, int64_t rows, float p0, float p1, co
   return JMT_OK;
 }
 
+// the *_perm entries' row map -> HeadArgs (P * Q = rows; the kernels walk it in 32 bits)
+static int head_perm_args(const char* name, int64_t rows, int64_t P, int64_t Q, HeadArgs* a) {
+  JMT_CHECK_ARG(rows < ((int64_t)1 << 31), "%s: rows = %lld (the row map walks 31 bits)", name,
+                (long long)rows);
+  JMT_CHECK_ARG(P >= 1 && Q >= 1 && P <= rows && Q <= rows && P * Q == rows,
+                "%s: row map P = %lld, Q = %lld does not tile rows = %lld (P * Q = rows)", name,
+                (long long)P, (long long)Q, (long long)rows);
+  a->P = P; a->Q = Q;
+  return JMT_OK;
+}
+
+// perm: the row map (P, Q) applies to y (the *_perm entries); else y is stored in h's row order
 static int head_fwd_impl(const char* name, int h_dt, int y_dt, int64_t rows, int hid, int k,
                          const void* h, int64_t ldh, const void* w2_0, const void* w2_1,
                          const float* b2_0, const float* b2_1, void* y_0, void* y_1, int64_t ldy,
-                         const HeadDrop* drop, void* stream) {
+                         bool perm, int64_t P, int64_t Q, const HeadDrop* drop, void* stream) {
   int rc = head_check(name, h_dt, rows, hid, k, h, ldh, w2_0, w2_1);
   if (rc != JMT_OK) return rc;
   JMT_CHECK_ARG(y_dt == JMT_F32 || y_dt == h_dt, "%s: y dtype", name);
@@ -297,17 +406,23 @@ static int head_fwd_impl(const char* name, int h_dt, int y_dt, int64_t rows, int
   if (rows == 0) return JMT_OK;
   HeadArgs a = {};
   a.h = h; a.ldh = ldh; a.w2[0] = w2_0; a.w2[1] = w2_1; a.b2[0] = b2_0; a.b2[1] = b2_1;
-  a.y[0] = y_0; a.y[1] = y_1; a.ldy = ldy; a.rows = rows; a.k = k;
+  a.y[0] = y_0; a.y[1] = y_1; a.ldy = ldy; a.rows = rows; a.k = k; a.P = rows; a.Q = 1;
+  if (perm && (rc = head_perm_args(name, rows, P, Q, &a)) != JMT_OK) return rc;
   HeadArgsDrop ad = {};
   (HeadArgs&)ad = a;
   if (drop) ad.dr = *drop;
   const dim3 grid(head_blocks(rows));
   hipStream_t st = as_stream(stream);
-#define HFWD1(TH, TY, K)                                                                   \
-  {                                                                                        \
-    if (drop)                                                                              \
-      hipLaunchKernelGGL((head_fwd_kernel<TH, TY, K, true>), grid, dim3(256), 0, st, ad);  \
-    else hipLaunchKernelGGL((head_fwd_kernel<TH, TY, K, false>), grid, dim3(256), 0, st, a); \
+#define HFWD2(TH, TY, K, PM)                                                                   \
+  {                                                                                            \
+    if (drop)                                                                                  \
+      hipLaunchKernelGGL((head_fwd_kernel<TH, TY, K, true, PM>), grid, dim3(256), 0, st, ad);  \
+    else hipLaunchKernelGGL((head_fwd_kernel<TH, TY, K, false, PM>), grid, dim3(256), 0, st, a); \
+  }
+#define HFWD1(TH, TY, K)              \
+  {                                   \
+    if (perm) HFWD2(TH, TY, K, true)  \
+    else HFWD2(TH, TY, K, false)      \
   }
 #define HFWD(TH, TY)                  \
   {                                   \
@@ -321,6 +436,7 @@ static int head_fwd_impl(const char* name, int h_dt, int y_dt, int64_t rows, int
   }
 #undef HFWD
 #undef HFWD1
+#undef HFWD2
   JMT_LAUNCH_CHECK(name);
   return JMT_OK;
 }
@@ -329,7 +445,15 @@ extern "C" int jmt_head_fwd(int h_dt, int y_dt, int64_t rows, int hid, int k, co
                             int64_t ldh, const void* w2_0, const void* w2_1, const float* b2_0,
                             const float* b2_1, void* y_0, void* y_1, int64_t ldy, void* stream) {
   return head_fwd_impl("jmt_head_fwd", h_dt, y_dt, rows, hid, k, h, ldh, w2_0, w2_1, b2_0, b2_1,
-                       y_0, y_1, ldy, nullptr, stream);
+                       y_0, y_1, ldy, false, 0, 0, nullptr, stream);
+}
+
+extern "C" int jmt_head_fwd_perm(int h_dt, int y_dt, int64_t rows, int hid, int k, const void* h,
+                                 int64_t ldh, const void* w2_0, const void* w2_1,
+                                 const float* b2_0, const float* b2_1, void* y_0, void* y_1,
+                                 int64_t ldy, int64_t P, int64_t Q, void* stream) {
+  return head_fwd_impl("jmt_head_fwd_perm", h_dt, y_dt, rows, hid, k, h, ldh, w2_0, w2_1, b2_0,
+                       b2_1, y_0, y_1, ldy, true, P, Q, nullptr, stream);
 }
 
 extern "C" int jmt_head_fwd_drop(int h_dt, int y_dt, int64_t rows, int hid, int k, const void* h,
@@ -341,14 +465,27 @@ extern "C" int jmt_head_fwd_drop(int h_dt, int y_dt, int64_t rows, int hid, int 
   int rc = head_drop_args("jmt_head_fwd_drop", rows, p0, p1, ctr, &dr);
   if (rc != JMT_OK) return rc;
   return head_fwd_impl("jmt_head_fwd_drop", h_dt, y_dt, rows, hid, k, h, ldh, w2_0, w2_1, b2_0,
-                       b2_1, y_0, y_1, ldy, &dr, stream);
+                       b2_1, y_0, y_1, ldy, false, 0, 0, &dr, stream);
 }
 
+extern "C" int jmt_head_fwd_perm_drop(int h_dt, int y_dt, int64_t rows, int hid, int k,
+                                      const void* h, int64_t ldh, const void* w2_0,
+                                      const void* w2_1, const float* b2_0, const float* b2_1,
+                                      void* y_0, void* y_1, int64_t ldy, int64_t P, int64_t Q,
+                                      float p0, float p1, const uint32_t* ctr, void* stream) {
+  HeadDrop dr = {};
+  int rc = head_drop_args("jmt_head_fwd_perm_drop", rows, p0, p1, ctr, &dr);
+  if (rc != JMT_OK) return rc;
+  return head_fwd_impl("jmt_head_fwd_perm_drop", h_dt, y_dt, rows, hid, k, h, ldh, w2_0, w2_1,
+                       b2_0, b2_1, y_0, y_1, ldy, true, P, Q, &dr, stream);
+}
+
+// perm: the row map (P, Q) applies to gy (the *_perm entries); dh keeps h's row order
 static int head_bwd_impl(const char* name, int h_dt, int gy_dt, int64_t rows, int hid, int k,
                          const void* h, int64_t ldh, const void* w2_0, const void* w2_1,
                          const void* gy_0, const void* gy_1, int64_t ldgy, void* dh, int64_t lddh,
                          float* dw2_0, float* dw2_1, float* db2_0, float* db2_1, float* partials,
-                         const HeadDrop* drop, void* stream) {
+                         bool perm, int64_t P, int64_t Q, const HeadDrop* drop, void* stream) {
   int rc = head_check(name, h_dt, rows, hid, k, h, ldh, w2_0, w2_1);
   if (rc != JMT_OK) return rc;
   JMT_CHECK_ARG(gy_dt == JMT_F32 || gy_dt == h_dt, "%s: gy dtype", name);
@@ -359,18 +496,26 @@ static int head_bwd_impl(const char* name, int h_dt, int gy_dt, int64_t rows, in
   a.h = h; a.ldh = ldh; a.w2[0] = w2_0; a.w2[1] = w2_1;
   a.gy[0] = gy_0; a.gy[1] = gy_1; a.ldgy = ldgy; a.dh = dh; a.lddh = lddh;
   a.partials = partials; a.dw2[0] = dw2_0; a.dw2[1] = dw2_1; a.db2[0] = db2_0; a.db2[1] = db2_1;
-  a.rows = rows; a.k = k;
+  a.rows = rows; a.k = k; a.P = rows; a.Q = 1;
+  if (perm && (rc = head_perm_args(name, rows, P, Q, &a)) != JMT_OK) return rc;
   HeadArgsDrop ad = {};
   (HeadArgs&)ad = a;
   if (drop) ad.dr = *drop;
   const int nblk = head_blocks(rows);
   hipStream_t st = as_stream(stream);
-#define HBWD1(TH, TG, K)                                                                  \
-  {                                                                                       \
-    if (drop)                                                                             \
-      hipLaunchKernelGGL((head_bwd_kernel<TH, TG, K, true>), dim3(nblk), dim3(256), 0, st, ad); \
-    else                                                                                  \
-      hipLaunchKernelGGL((head_bwd_kernel<TH, TG, K, false>), dim3(nblk), dim3(256), 0, st, a); \
+#define HBWD2(TH, TG, K, PM)                                                                  \
+  {                                                                                           \
+    if (drop)                                                                                 \
+      hipLaunchKernelGGL((head_bwd_kernel<TH, TG, K, true, PM>), dim3(nblk), dim3(256), 0, st, \
+                         ad);                                                                 \
+    else                                                                                      \
+      hipLaunchKernelGGL((head_bwd_kernel<TH, TG, K, false, PM>), dim3(nblk), dim3(256), 0, st, \
+                         a);                                                                  \
+  }
+#define HBWD1(TH, TG, K)              \
+  {                                   \
+    if (perm) HBWD2(TH, TG, K, true)  \
+    else HBWD2(TH, TG, K, false)      \
   }
 #define HBWD(TH, TG)                  \
   {                                   \
@@ -384,6 +529,7 @@ static int head_bwd_impl(const char* name, int h_dt, int gy_dt, int64_t rows, in
   }
 #undef HBWD
 #undef HBWD1
+#undef HBWD2
   JMT_LAUNCH_CHECK(name);
   if (dw2_0 || dw2_1 || db2_0 || db2_1) {
     const int SK = k * (HD_HID + 1);
@@ -399,7 +545,19 @@ extern "C" int jmt_head_bwd(int h_dt, int gy_dt, int64_t rows, int hid, int k, c
                             float* dw2_1, float* db2_0, float* db2_1, float* partials,
                             void* stream) {
   return head_bwd_impl("jmt_head_bwd", h_dt, gy_dt, rows, hid, k, h, ldh, w2_0, w2_1, gy_0, gy_1,
-                       ldgy, dh, lddh, dw2_0, dw2_1, db2_0, db2_1, partials, nullptr, stream);
+                       ldgy, dh, lddh, dw2_0, dw2_1, db2_0, db2_1, partials, false, 0, 0, nullptr,
+                       stream);
+}
+
+extern "C" int jmt_head_bwd_perm(int h_dt, int gy_dt, int64_t rows, int hid, int k, const void* h,
+                                 int64_t ldh, const void* w2_0, const void* w2_1,
+                                 const void* gy_0, const void* gy_1, int64_t ldgy, void* dh,
+                                 int64_t lddh, float* dw2_0, float* dw2_1, float* db2_0,
+                                 float* db2_1, float* partials, int64_t P, int64_t Q,
+                                 void* stream) {
+  return head_bwd_impl("jmt_head_bwd_perm", h_dt, gy_dt, rows, hid, k, h, ldh, w2_0, w2_1, gy_0,
+                       gy_1, ldgy, dh, lddh, dw2_0, dw2_1, db2_0, db2_1, partials, true, P, Q,
+                       nullptr, stream);
 }
 
 extern "C" int jmt_head_bwd_drop(int h_dt, int gy_dt, int64_t rows, int hid, int k, const void* h,
@@ -412,5 +570,21 @@ extern "C" int jmt_head_bwd_drop(int h_dt, int gy_dt, int64_t rows, int hid, int
   int rc = head_drop_args("jmt_head_bwd_drop", rows, p0, p1, ctr, &dr);
   if (rc != JMT_OK) return rc;
   return head_bwd_impl("jmt_head_bwd_drop", h_dt, gy_dt, rows, hid, k, h, ldh, w2_0, w2_1, gy_0,
-                       gy_1, ldgy, dh, lddh, dw2_0, dw2_1, db2_0, db2_1, partials, &dr, stream);
+                       gy_1, ldgy, dh, lddh, dw2_0, dw2_1, db2_0, db2_1, partials, false, 0, 0, &dr,
+                       stream);
+}
+
+extern "C" int jmt_head_bwd_perm_drop(int h_dt, int gy_dt, int64_t rows, int hid, int k,
+                                      const void* h, int64_t ldh, const void* w2_0,
+                                      const void* w2_1, const void* gy_0, const void* gy_1,
+                                      int64_t ldgy, void* dh, int64_t lddh, float* dw2_0,
+                                      float* dw2_1, float* db2_0, float* db2_1, float* partials,
+                                      int64_t P, int64_t Q, float p0, float p1,
+                                      const uint32_t* ctr, void* stream) {
+  HeadDrop dr = {};
+  int rc = head_drop_args("jmt_head_bwd_perm_drop", rows, p0, p1, ctr, &dr);
+  if (rc != JMT_OK) return rc;
+  return head_bwd_impl("jmt_head_bwd_perm_drop", h_dt, gy_dt, rows, hid, k, h, ldh, w2_0, w2_1,
+                       gy_0, gy_1, ldgy, dh, lddh, dw2_0, dw2_1, db2_0, db2_1, partials, true, P, Q,
+                       &dr, stream);
 }

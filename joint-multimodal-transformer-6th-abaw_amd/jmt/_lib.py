@@ -253,6 +253,25 @@ _PROTOS = {
                                    C.c_double, c_f, c_f, c_f, c_vp, c_int, c_vp, c_int, c_vp]),
     "jmt_sgd_step_dev_clip": (c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_int, c_int,
                                       c_f, c_vp, c_int, c_vp, c_int, c_vp]),
+    # the head entries with the row map (P, Q) on y / gy before the stream (the *_perm_drop ones:
+    # before (p0, p1, ctr)): y in the logical (T, B) order, no transposing copy
+    "jmt_head_fwd_perm": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "jmt_head_bwd_perm": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp,
+                                  c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_i64, c_i64, c_vp]),
+    "jmt_head_fwd_perm_drop": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f,
+                                       c_f, c_vp, c_vp]),
+    "jmt_head_bwd_perm_drop": (c_int, [c_int, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp,
+                                       c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp, c_i64, c_i64, c_f, c_f, c_vp, c_vp]),
+    # jmt_ccc_stats + jmt_ccc_finish(_add) of one rank in one launch: jmt_ccc_stats' arguments
+    # up to stats, then (bs, eps, [add,] loss, coef, stream)
+    "jmt_ccc_stats_finish": (c_int, [c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f, c_f, c_f, c_vp,
+                                     c_i64, c_f, c_vp, c_vp, c_vp]),
+    "jmt_ccc_stats_finish_add": (c_int, [c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f, c_f, c_f,
+                                         c_vp, c_i64, c_f, c_vp, c_vp, c_vp, c_vp]),
 }
 
 EXPORTED = tuple(_PROTOS)

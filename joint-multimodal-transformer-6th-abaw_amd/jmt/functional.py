@@ -263,6 +263,33 @@ def wgrad_scope(cd=torch.float32):
         contextlib.nullcontext()
 
 
+# ------------------------------------------------------------------------- preallocated outputs
+class Into:
+    """A preallocated output (`out=` of linear / l2_normalize) handed to a Function as a plain
+    Python object: autograd does not see it as an input, so the result is an ordinary fresh output
+    that lives in the caller's buffer — no in-place bookkeeping, and no earlier value of the
+    buffer is read by anyone.  The producers save their inputs, never their outputs, so a buffer
+    that several producers fill slot by slot (grouped.JointSlots) invalidates no saved tensor."""
+    __slots__ = ("t",)
+
+    def __init__(self, t: torch.Tensor):
+        self.t = t
+
+
+def _into(out: Optional[Into], L: Rows, F2: int, dtype: torch.dtype, who: str) -> torch.Tensor:
+    """The tensor of `out` after checking that it is what L.like(F2, dtype) would allocate for
+    rows in their logical order: same shape and dtype, contiguous, 16-B aligned; else L.like."""
+    if out is None:
+        return L.like(F2, dtype)
+    y = out.t
+    if (list(L.perm) != sorted(L.perm) or tuple(y.shape) != L.shape[:-1] + (F2,) or
+            y.dtype != dtype or y.device != L.t.device or not y.is_contiguous() or
+            y.data_ptr() % 16 or (F2 > 1 and F2 % _vec(dtype))):
+        raise JMTError(f"{who}: out= must be a contiguous, 16-B aligned {dtype} tensor of shape "
+                       f"{L.shape[:-1] + (F2,)} for an input whose rows are in logical order")
+    return y
+
+
 # ------------------------------------------------------------------------- Linear
 class LinearFn(Function):
     """y = cat(xs, -1) @ W[r0:r0+n]^T + b[r0:r0+n]
@@ -273,7 +300,7 @@ class LinearFn(Function):
     mm_multi_transformers.py:120-124, 201-211; mm_transformers.py:140-144; FeatureConcatFC)."""
 
     @staticmethod
-    def forward(ctx, W, b, r0, n, out_dtype, *xs):
+    def forward(ctx, W, b, r0, n, out_dtype, out, *xs):
         cd = compute_dtype()
         lay = [Rows(x, cd) for x in xs]
         L0 = lay[0]
@@ -284,7 +311,7 @@ class LinearFn(Function):
         if len(lay) > 1 and kseg % (32 if cd == torch.float32 else 64):
             raise RuntimeError("LinearFn: concat segment width must be a multiple of 64")
         odt = out_dtype if out_dtype is not None else cd
-        y = L0.like(n, odt)
+        y = _into(out, L0, n, odt, "linear")
         xin = [l.t for l in lay]
         lg.fwd(lg.kcat(xin, L0.ld, kseg), L0.rows, W, b, _out(y, L0.perm), cd, r0, n)
         ctx.save_for_backward(W, b, *xin)
@@ -299,7 +326,7 @@ class LinearFn(Function):
         Gy = _match(gy, Rows(L0.like(n, cd)), cd)
         nseg = len(xin)
         dxs = [None] * nseg
-        need = [ctx.needs_input_grad[5 + i] for i in range(nseg)]
+        need = [ctx.needs_input_grad[6 + i] for i in range(nseg)]
         if any(need):
             outs = [L0.like(kseg, cd) for _ in range(nseg)]
             lg.dgrad(Gy.op(), Gy.rows, n, W, lg.table(outs, _ld(outs[0], L0.perm)), cd, r0, kseg)
@@ -315,15 +342,16 @@ class LinearFn(Function):
                      defer=not any(need))
 
         streams.run_side(param_grads, reads=(Gy.t,) + tuple(xin))
-        return (None, None, None, None, None, *dxs)
+        return (None, None, None, None, None, None, *dxs)
 
 
-def linear(xs, W, b=None, r0=0, n=None, out_dtype=None):
+def linear(xs, W, b=None, r0=0, n=None, out_dtype=None, out=None):
+    """out: a preallocated tensor the GEMM writes (the layout the call would allocate itself)."""
     if isinstance(xs, torch.Tensor):
         xs = (xs,)
     if n is None:
         n = W.shape[0]
-    return LinearFn.apply(W, b, r0, n, out_dtype, *xs)
+    return LinearFn.apply(W, b, r0, n, out_dtype, Into(out) if out is not None else None, *xs)
 
 
 # ------------------------------------------------------------------------- regressor dropout
@@ -467,6 +495,41 @@ _pair_mlp = {"on": os.environ.get("JMT_PAIR_MLP", "1") != "0"}
 _fused_head_on = {"on": os.environ.get("JMT_FUSED_HEAD", "1") != "0"}
 
 
+# A/B switches of the head / loss tail (each default on; 0 = the launches it replaced):
+#   JMT_HEAD_PERM         the fused head writes seq-first predictions in their logical order
+#                         (jmt_head_*_perm) instead of a transposing copy after it
+#   JMT_CCC_FUSED_FINISH  one-rank CCC losses: statistics and finish in one launch
+#   JMT_STACK_INPLACE     the video projection and the normalised audio are written into their
+#                         slots of the stacked X (models/two_transformers.py, grouped.StackJointFn)
+_tail = {"head_perm": os.environ.get("JMT_HEAD_PERM", "1") != "0",
+         "ccc_fused_finish": os.environ.get("JMT_CCC_FUSED_FINISH", "1") != "0",
+         "stack_inplace": os.environ.get("JMT_STACK_INPLACE", "1") != "0"}
+
+
+def head_perm_enabled() -> bool:
+    return _tail["head_perm"]
+
+
+def set_head_perm(on: bool) -> None:
+    _tail["head_perm"] = bool(on)
+
+
+def ccc_fused_finish_enabled() -> bool:
+    return _tail["ccc_fused_finish"]
+
+
+def set_ccc_fused_finish(on: bool) -> None:
+    _tail["ccc_fused_finish"] = bool(on)
+
+
+def stack_inplace_enabled() -> bool:
+    return _tail["stack_inplace"]
+
+
+def set_stack_inplace(on: bool) -> None:
+    _tail["stack_inplace"] = bool(on)
+
+
 def pair_mlps_enabled() -> bool:
     """Two_transformers runs its V / A regressors as one MLPPairFn (JMT_PAIR_MLP=0: two MLPFn)."""
     return _pair_mlp["on"]
@@ -499,8 +562,17 @@ class MLPPairFn(Function):
         # both first layers: one launch writing [h_a | h_b] side by side
         lg.fwd(L.op(), L.rows, (W1a, W1b), (b1a, b1b), lg.strided(h, ldh, hid), cd, relu=True)
         odt = out_dtype if out_dtype is not None else cd
-        ys = [L.like(nout, odt), L.like(nout, odt)]
         fused = MLPPairFn._fused_head(cd, hid, nout)
+        # x seq-first over batch-first rows (the FC head's av): the head kernels store the
+        # outputs in their logical order, contiguous, through the row map pq
+        pq = MLPPairFn._head_perm(L) if fused else None
+        if pq is not None:
+            ys = [torch.empty(L.shape[:-1] + (nout,), dtype=odt, device=h.device)
+                  for _ in range(2)]
+            ldy = nout
+        else:
+            ys = [L.like(nout, odt), L.like(nout, odt)]
+            ldy = _ld(ys[0], L.perm)
         W2c = [weight_as(W2a, cd), weight_as(W2b, cd)] if fused else None
         ctr = None
         if p_a > 0.0 or p_b > 0.0:
@@ -508,18 +580,28 @@ class MLPPairFn(Function):
             if not fused:
                 ops.dropout(h, ldh, h, ldh, L.rows, 2 * hid, hid, p_a, p_b, ctr)
         if fused and ctr is not None:
-            ops.head_fwd_drop(h, ldh, L.rows, nout, W2c, (b2a, b2b), ys, _ld(ys[0], L.perm),
-                              p_a, p_b, ctr)
+            ops.head_fwd_drop(h, ldh, L.rows, nout, W2c, (b2a, b2b), ys, ldy, p_a, p_b, ctr,
+                              perm=pq)
         elif fused:
             # both second layers as one row kernel over [h_a | h_b] (csrc/head.hip)
-            ops.head_fwd(h, ldh, L.rows, nout, W2c, (b2a, b2b), ys, _ld(ys[0], L.perm))
+            ops.head_fwd(h, ldh, L.rows, nout, W2c, (b2a, b2b), ys, ldy, perm=pq)
         else:
             # both second layers: one GEMM launch over the halves of h (2-entry tables)
             lg.fwd(lg.strided(h, ldh, hid), L.rows, (W2a, W2b), (b2a, b2b),
                    lg.table(ys, _ld(ys[0], L.perm)), cd)
         ctx.save_for_backward(W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, L.t, h, ctr)
-        ctx.meta = (cd, L, x.dtype, odt, fused, p_a, p_b)
+        ctx.meta = (cd, L, x.dtype, odt, fused, p_a, p_b, pq)
         return ys[0], ys[1]
+
+    @staticmethod
+    def _head_perm(L: Rows):
+        """(P, Q) of the head kernels' row map when the two leading dims of x are a transposition
+        of its row order in memory (logical (T, B), rows r = b T + t: P = T, Q = B), else None
+        (JMT_HEAD_PERM=0: always None, the outputs keep x's row order)."""
+        if not _tail["head_perm"] or list(L.perm) != [1, 0] or L.rows >= 1 << 31:
+            return None
+        T, B = L.shape[0], L.shape[1]
+        return (T, B) if T > 1 and B > 1 else None
 
     @staticmethod
     def _fused_head(cd, hid, nout) -> bool:
@@ -547,7 +629,7 @@ class MLPPairFn(Function):
     @once_differentiable
     def backward(ctx, gya, gyb):
         W1a, b1a, W2a, b2a, W1b, b1b, W2b, b2b, xin, h, ctr = ctx.saved_tensors
-        cd, L, xdt, odt, fused, p_a, p_b = ctx.meta
+        cd, L, xdt, odt, fused, p_a, p_b, pq = ctx.meta
         hid, nout = W1a.shape[0], W2a.shape[0]
         dev = h.device
         ldh = _ld(h, L.perm)
@@ -570,18 +652,25 @@ class MLPPairFn(Function):
             # K-concatenated GEMM dx = [dh_a | dh_b] [W1a; W1b] (one rounding of the sum of both
             # heads' contributions, no separate add)
             gdt = torch.float32 if odt == torch.float32 else cd
-            G2 = [_match(gy, Rows(L.like(nout, gdt)), gdt) for gy in gys]
-            if G2[1].ld != G2[0].ld or G2[1].perm != G2[0].perm:
-                G2[1] = _match(G2[1].t, G2[0], gdt)
+            if pq is not None:
+                # the gradients of the logically contiguous outputs, read through the forward's
+                # row map as they arrive (no re-layout into x's row order)
+                gts = [gy if gy.dtype == gdt and gy.is_contiguous() else
+                       gy.to(gdt).contiguous() for gy in gys]
+                ldg = nout
+            else:
+                G2 = [_match(gy, Rows(L.like(nout, gdt)), gdt) for gy in gys]
+                if G2[1].ld != G2[0].ld or G2[1].perm != G2[0].perm:
+                    G2[1] = _match(G2[1].t, G2[0], gdt)
+                gts, ldg = [G.t for G in G2], G2[0].ld
             W2c = [weight_as(W2a, cd), weight_as(W2b, cd)]
             dw2 = [_grad_buffer(W2a), _grad_buffer(W2b)]
             db2 = [_grad_buffer(b2a), _grad_buffer(b2b)]
             if ctr is not None:
-                ops.head_bwd_drop(h, ldh, L.rows, nout, W2c, [G.t for G in G2], G2[0].ld, dh,
-                                  ldh, dw2, db2, p_a, p_b, ctr)
+                ops.head_bwd_drop(h, ldh, L.rows, nout, W2c, gts, ldg, dh, ldh, dw2, db2, p_a,
+                                  p_b, ctr, perm=pq)
             else:
-                ops.head_bwd(h, ldh, L.rows, nout, W2c, [G.t for G in G2], G2[0].ld, dh, ldh,
-                             dw2, db2)
+                ops.head_bwd(h, ldh, L.rows, nout, W2c, gts, ldg, dh, ldh, dw2, db2, perm=pq)
             _grad_done(W2a, W2b, b2a, b2b)
             dx = None
             if ctx.needs_input_grad[9]:
@@ -648,10 +737,10 @@ class L2NormFn(Function):
     """F.normalize(x, p=2, dim=-1, eps=1e-12) (two_transformers.py:118-119)."""
 
     @staticmethod
-    def forward(ctx, x, eps):
+    def forward(ctx, x, eps, out=None):
         cd = compute_dtype()
         L = Rows(x)
-        y = L.like(L.F, cd)
+        y = _into(out, L, L.F, cd, "l2_normalize")
         inv = torch.empty(L.rows, dtype=torch.float32, device=x.device)
         ops.l2norm_fwd(L.t, L.ld, L.rows, L.F, y, _ld(y, L.perm), inv, eps)
         ctx.save_for_backward(L.t, inv)
@@ -665,11 +754,12 @@ class L2NormFn(Function):
         G = _match(gy, Rows(L.like(L.F, cd)), cd)
         dx = L.like(L.F, x.dtype)
         ops.l2norm_bwd(x, L.ld, G.t, G.ld, inv, eps, dx, _ld(dx, L.perm), L.rows, L.F)
-        return dx, None
+        return dx, None, None
 
 
-def l2_normalize(x, eps=1e-12):
-    return L2NormFn.apply(x, eps)
+def l2_normalize(x, eps=1e-12, out=None):
+    """out: a preallocated tensor the kernel writes (the layout the call would allocate itself)."""
+    return L2NormFn.apply(x, eps, Into(out) if out is not None else None)
 
 
 # ------------------------------------------------------------------------- residual LayerNorm
@@ -1303,23 +1393,28 @@ class CCCLossFn(Function):
         elif lab.dtype != torch.float32 or not lab.is_contiguous():
             lab = ops.cast(lab, torch.float32)
         stats = torch.empty(8, dtype=torch.float64, device=dev)
-        ops.ccc_stats(kind, pred_c, lab, k, ignore, lo, hi, stats)
+        if add is not None and (add.dtype != torch.float32 or add.numel() != 1):
+            raise ValueError("ccc loss: `add` must be an fp32 scalar")
         world = 1
-        stats_all = stats
         if group is not None:
             import torch.distributed as dist
             world = dist.get_world_size(group)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        coef = torch.empty(8, dtype=torch.float64, device=dev)
+        if world == 1 and _tail["ccc_fused_finish"]:
+            # one rank: nothing to gather between the statistics and the finish — one launch
+            ops.ccc_stats_finish(kind, pred_c, lab, k, ignore, lo, hi, stats, bs, eps, loss, coef,
+                                 add=add)
+        else:
+            ops.ccc_stats(kind, pred_c, lab, k, ignore, lo, hi, stats)
+            stats_all = stats
             if world > 1:
                 from .graph import collective
                 stats_all = torch.empty(8 * world, dtype=torch.float64, device=dev)
                 # on the host between two segment replays under a SegmentedStep capture
                 collective(lambda sa=stats_all, st=stats:
                            dist.all_gather_into_tensor(sa, st, group=group))
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        coef = torch.empty(8, dtype=torch.float64, device=dev)
-        if add is not None and (add.dtype != torch.float32 or add.numel() != 1):
-            raise ValueError("ccc loss: `add` must be an fp32 scalar")
-        ops.ccc_finish(kind, world, stats_all, bs, eps, loss, coef, add=add)
+            ops.ccc_finish(kind, world, stats_all, bs, eps, loss, coef, add=add)
         ctx.save_for_backward(pred_c, lab, coef)
         ctx.meta = (kind, k, ignore, lo, hi, pred.shape, add.shape if add is not None else None)
         return loss

@@ -108,20 +108,48 @@ def stack_groups(*xs) -> torch.Tensor:
     return StackGroupsFn.apply(*xs)
 
 
+class JointSlots:
+    """StackJointFn's stacked (3, B, T, E) buffer allocated ahead of its producers: they write the
+    two streams into slot(0) and slot(1) (`out=` of linear / l2_normalize), and StackJointFn, given
+    this object, copies only an input that is not already its slot.  A plain Python object:
+    autograd sees the buffer first as StackJointFn's output."""
+
+    def __init__(self, B: int, T: int, E: int, device):
+        self.X = torch.empty(3, B, T, E, dtype=compute_dtype(), device=device)
+
+    def slot(self, g: int) -> torch.Tensor:
+        return self.X[g]
+
+
+def _is_slot(x: torch.Tensor, s: torch.Tensor) -> bool:
+    """x already is the slot s: same storage, offset, shape, strides and dtype."""
+    return (x.dtype == s.dtype and x.device == s.device and
+            x.untyped_storage().data_ptr() == s.untyped_storage().data_ptr() and
+            x.storage_offset() == s.storage_offset() and x.shape == s.shape and
+            x.stride() == s.stride())
+
+
 class StackJointFn(Function):
     """X = stack(v, p, cat(v, p) W^T + b) -> (3, B, T, E): the two streams and the joint
     representation of out_layer_pv (mm_multi_transformers.py:120-124) in one stacked buffer;
     the K-concatenated GEMM writes the third slot directly.  The backward adds out_layer_pv's
     input gradients into the first two slots of the incoming dX with the dgrad GEMM's beta = 1
-    epilogue, so the two uses of v and p need no separate gradient sum."""
+    epilogue, so the two uses of v and p need no separate gradient sum.  slots (JointSlots): X
+    is the caller's buffer, and an input that already is its slot is not copied."""
 
     @staticmethod
-    def forward(ctx, v, p, W, b):
+    def forward(ctx, v, p, W, b, slots=None):
         cd = compute_dtype()
         B, T, E = v.shape
         assert tuple(p.shape) == (B, T, E) and W.shape == (E, 2 * E), (v.shape, p.shape, W.shape)
-        X = torch.empty(3, B, T, E, dtype=cd, device=v.device)
+        if slots is not None and tuple(slots.X.shape) == (3, B, T, E) and slots.X.dtype == cd \
+                and slots.X.device == v.device and slots.X.is_contiguous():
+            X = slots.X
+        else:
+            X = torch.empty(3, B, T, E, dtype=cd, device=v.device)
         for g, x in enumerate((v, p)):
+            if _is_slot(x, X[g]):
+                continue
             if x.stride(-1) != 1 or x.stride(1) != E * x.stride(2) or \
                     x.stride(0) != T * x.stride(1):
                 x = x.contiguous()
@@ -147,11 +175,11 @@ class StackJointFn(Function):
         lg.wgrad(G.op(), lg.table([X[0], X[1]], E), G.rows, E, W, cd, b, kseg=E, defer=True)
         dv = dX[0] if vdt == cd else _cast_keep_layout(dX[0], vdt)
         dp = dX[1] if pdt == cd else _cast_keep_layout(dX[1], pdt)
-        return dv, dp, None, None
+        return dv, dp, None, None, None
 
 
-def stack_joint(v, p, W, b) -> torch.Tensor:
-    return StackJointFn.apply(v, p, W, b)
+def stack_joint(v, p, W, b, slots=None) -> torch.Tensor:
+    return StackJointFn.apply(v, p, W, b, slots)
 
 
 class StackTokensFn(Function):

@@ -28,8 +28,8 @@ class Linear(nn.Module):
             bound = 1 / math.sqrt(self.in_features) if self.in_features > 0 else 0
             nn.init.uniform_(self.bias, -bound, bound)
 
-    def forward(self, x, out_dtype=None):
-        return F.linear(x, self.weight, self.bias, out_dtype=out_dtype)
+    def forward(self, x, out_dtype=None, out=None):
+        return F.linear(x, self.weight, self.bias, out_dtype=out_dtype, out=out)
 
     def extra_repr(self):
         return f"in_features={self.in_features}, out_features={self.out_features}"

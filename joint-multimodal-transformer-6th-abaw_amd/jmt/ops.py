@@ -918,26 +918,43 @@ def ccc_finish(kind, world, stats_all, bs, eps, loss, coef, add=None):
                   add.data_ptr(), loss.data_ptr(), coef.data_ptr(), stream())
 
 
+def ccc_stats_finish(kind, pred, label, k, ignore, lo, hi, stats, bs, eps, loss, coef, add=None):
+    """ccc_stats then ccc_finish(world = 1) on those statistics as one launch
+    (jmt_ccc_stats_finish / _add): the same stats, loss and coef."""
+    n = label.numel()
+    head = (kind, dt(pred), n, k, pred.data_ptr(), label.data_ptr(), ignore, lo, hi,
+            stats.data_ptr(), bs, eps)
+    if add is None:
+        _lib.call("jmt_ccc_stats_finish", *head, loss.data_ptr(), coef.data_ptr(), stream())
+    else:
+        _lib.call("jmt_ccc_stats_finish_add", *head, add.data_ptr(), loss.data_ptr(),
+                  coef.data_ptr(), stream())
+
+
 HEAD_HID, HEAD_KMAX = 128, 24      # csrc/head.hip
 
 
-def head_fwd(h, ldh, rows, k, w2, b2, ys, ldy):
-    """Both regressors' output layers (csrc/head.hip jmt_head_fwd)."""
+def head_fwd(h, ldh, rows, k, w2, b2, ys, ldy, perm=None):
+    """Both regressors' output layers (csrc/head.hip jmt_head_fwd).  perm = (P, Q): memory row r
+    of h is stored at row (r mod P) * Q + r div P of ys (jmt_head_fwd_perm)."""
     p = lambda t: t.data_ptr() if t is not None else None
-    _lib.call("jmt_head_fwd", dt(h), dt(ys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
+    name, pq = ("jmt_head_fwd", ()) if perm is None else ("jmt_head_fwd_perm", tuple(perm))
+    _lib.call(name, dt(h), dt(ys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
               w2[0].data_ptr(), w2[1].data_ptr(), p(b2[0]), p(b2[1]), ys[0].data_ptr(),
-              ys[1].data_ptr(), ldy, stream())
+              ys[1].data_ptr(), ldy, *pq, stream())
 
 
-def head_bwd(h, ldh, rows, k, w2, gys, ldgy, dh, lddh, dw2, db2):
-    """dh (ReLU-masked) and += weight / bias gradients of both output layers (jmt_head_bwd)."""
+def head_bwd(h, ldh, rows, k, w2, gys, ldgy, dh, lddh, dw2, db2, perm=None):
+    """dh (ReLU-masked) and += weight / bias gradients of both output layers (jmt_head_bwd).
+    perm = (P, Q): gys are read through head_fwd's row map (jmt_head_bwd_perm)."""
     p = lambda t: t.data_ptr() if t is not None else None
     nbytes = _lib.load().jmt_head_bwd_workspace_bytes(rows)
     ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=h.device)
-    _lib.call("jmt_head_bwd", dt(h), dt(gys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
+    name, pq = ("jmt_head_bwd", ()) if perm is None else ("jmt_head_bwd_perm", tuple(perm))
+    _lib.call(name, dt(h), dt(gys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
               w2[0].data_ptr(), w2[1].data_ptr(), gys[0].data_ptr(), gys[1].data_ptr(), ldgy,
               dh.data_ptr(), lddh, p(dw2[0]), p(dw2[1]), p(db2[0]), p(db2[1]), ws.data_ptr(),
-              stream())
+              *pq, stream())
 
 
 # ------------------------------------------------------------------------------------ dropout
@@ -970,23 +987,27 @@ def dropout_reference(ctr, rows, cols, split, p0, p1):
     return out
 
 
-def head_fwd_drop(h, ldh, rows, k, w2, b2, ys, ldy, p0, p1, ctr):
-    """head_fwd on the dropout-masked hidden activations (jmt_head_fwd_drop)."""
+def head_fwd_drop(h, ldh, rows, k, w2, b2, ys, ldy, p0, p1, ctr, perm=None):
+    """head_fwd on the dropout-masked hidden activations (jmt_head_fwd_drop / _perm_drop)."""
     p = lambda t: t.data_ptr() if t is not None else None
-    _lib.call("jmt_head_fwd_drop", dt(h), dt(ys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
+    name, pq = ("jmt_head_fwd_drop", ()) if perm is None else \
+        ("jmt_head_fwd_perm_drop", tuple(perm))
+    _lib.call(name, dt(h), dt(ys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
               w2[0].data_ptr(), w2[1].data_ptr(), p(b2[0]), p(b2[1]), ys[0].data_ptr(),
-              ys[1].data_ptr(), ldy, float(p0), float(p1), ctr.data_ptr(), stream())
+              ys[1].data_ptr(), ldy, *pq, float(p0), float(p1), ctr.data_ptr(), stream())
 
 
-def head_bwd_drop(h, ldh, rows, k, w2, gys, ldgy, dh, lddh, dw2, db2, p0, p1, ctr):
-    """head_bwd with the forward's mask regenerated from `ctr` (jmt_head_bwd_drop)."""
+def head_bwd_drop(h, ldh, rows, k, w2, gys, ldgy, dh, lddh, dw2, db2, p0, p1, ctr, perm=None):
+    """head_bwd with the forward's mask regenerated from `ctr` (jmt_head_bwd_drop / _perm_drop)."""
     p = lambda t: t.data_ptr() if t is not None else None
     nbytes = _lib.load().jmt_head_bwd_workspace_bytes(rows)
     ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=h.device)
-    _lib.call("jmt_head_bwd_drop", dt(h), dt(gys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
+    name, pq = ("jmt_head_bwd_drop", ()) if perm is None else \
+        ("jmt_head_bwd_perm_drop", tuple(perm))
+    _lib.call(name, dt(h), dt(gys[0]), rows, HEAD_HID, k, h.data_ptr(), ldh,
               w2[0].data_ptr(), w2[1].data_ptr(), gys[0].data_ptr(), gys[1].data_ptr(), ldgy,
               dh.data_ptr(), lddh, p(dw2[0]), p(dw2[1]), p(db2[0]), p(db2[1]), ws.data_ptr(),
-              float(p0), float(p1), ctr.data_ptr(), stream())
+              *pq, float(p0), float(p1), ctr.data_ptr(), stream())
 
 
 def ce_stats(x, label, k, lo, hi, weights, stats):

@@ -132,10 +132,14 @@ class MultimodalTransformer_w_JR(nn.Module):
         else:
             raise NotImplementedError(output_format)
 
-    def forward(self, visual_features, physiological_features, key_padding_mask=None):
+    def forward(self, visual_features, physiological_features, key_padding_mask=None,
+                joint_slots=None):
+        # joint_slots (an extra keyword, grouped.JointSlots): the caller had the two inputs
+        # written into the grouped path's stacked buffer, which then copies neither
         kr = F.key_ranges(key_padding_mask) if key_padding_mask is not None else None
         if grouped.enabled() and visual_features.shape == physiological_features.shape:
-            return self._forward_grouped(visual_features, physiological_features, kr)
+            return self._forward_grouped(visual_features, physiological_features, kr,
+                                         joint_slots)
         # cat + out_layer_pv as ONE K-concatenated GEMM (:120-124)
         joint_representation = F.linear((visual_features, physiological_features),
                                         self.out_layer_pv.weight, self.out_layer_pv.bias)
@@ -175,13 +179,14 @@ class MultimodalTransformer_w_JR(nn.Module):
         # FC head (:201-211): torch.cat of the 6 outputs never materialised (K-concat GEMM)
         return F.linear(tuple(outs), self.out_layer1.weight, self.out_layer1.bias)
 
-    def _forward_grouped(self, visual_features, physiological_features, kr=None):
+    def _forward_grouped(self, visual_features, physiological_features, kr=None,
+                         joint_slots=None):
         """Same math, batched across the parallel branches (jmt/grouped.py): the three streams
         in one stacked (3, B, T, E) buffer — out_layer_pv's K-concatenated GEMM (:120-124)
         writing the joint representation into its third slot — each encoder layer of the three
         encoders as one grouped launch sequence, the six cross-attentions as one (:132-167)."""
         X = grouped.stack_joint(visual_features, physiological_features,
-                                self.out_layer_pv.weight, self.out_layer_pv.bias)
+                                self.out_layer_pv.weight, self.out_layer_pv.bias, joint_slots)
         krk = {} if kr is None else {"kr": kr}      # without a mask: the calls of before
         for lv, lp, lj in zip(self.visual_encoder.layers, self.physiological_encoder.layers,
                               self.joint_representation_encoder.layers):

@@ -7,6 +7,7 @@ import torch
 from torch import nn
 
 from jmt import functional as F
+from jmt import grouped
 from jmt import taps
 from jmt.nn import Linear, MLP
 
@@ -77,18 +78,42 @@ class Two_transformers(nn.Module):
         self.vregressor = MLP(dim, 128, digitize_num, dropout=v_dropout)
         self.aregressor = MLP(dim, 128, digitize_num, dropout=a_dropout)
 
+    def _joint_slots(self, f1_norm, f2_norm):
+        """The stacked buffer of the grouped TRANSFORMER fusion (jmt.grouped.JointSlots) when the
+        forward will take that path on (B, T, 512) streams, else None (JMT_STACK_INPLACE=0:
+        always None)."""
+        if not (F.stack_inplace_enabled() and self.joint_modalities == 'TRANSFORMER' and
+                grouped.enabled() and f1_norm.dim() == 3 and f2_norm.dim() == 3 and
+                f1_norm.shape[:2] == f2_norm.shape[:2] and f1_norm.shape[2] == 512 and
+                f1_norm.is_contiguous() and f2_norm.is_contiguous() and
+                (self.linear is not None or f2_norm.shape[2] == 512)):
+            return None
+        B, T = f1_norm.shape[:2]
+        return grouped.JointSlots(B, T, 512, f1_norm.device)
+
     def forward(self, f1_norm, f2_norm, key_padding_mask=None):
         # key_padding_mask (an extra keyword, default off): (B, T) bool, True = padded frame (the
         # reference's collate left-pads short clips with zero frames and labels them -5.0); the
         # time-axis attentions of the TRANSFORMER fusion then ignore those frames as keys
-        video = F.l2_normalize(f2_norm)          # :118
-        audio = F.l2_normalize(f1_norm)          # :119
-        if self.linear is not None:
-            video = self.linear(video)           # :120-121
+        slots = self._joint_slots(f1_norm, f2_norm)
+        kw = {}
+        if slots is None:
+            video = F.l2_normalize(f2_norm)          # :118
+            audio = F.l2_normalize(f1_norm)          # :119
+            if self.linear is not None:
+                video = self.linear(video)           # :120-121
+        else:
+            # the grouped fusion stacks (video, audio, joint) in one buffer: the two producers
+            # write their slots of it directly instead of being copied there
+            kw = {"joint_slots": slots}
+            video = F.l2_normalize(f2_norm, out=None if self.linear is not None else slots.slot(0))
+            audio = F.l2_normalize(f1_norm, out=slots.slot(1))
+            if self.linear is not None:
+                video = self.linear(video, out=slots.slot(0))
         if key_padding_mask is None or self.joint_modalities == 'FC':    # 'FC': no attention
-            av = self.mm_transformer(video, audio)
+            av = self.mm_transformer(video, audio, **kw)
         elif self.joint_modalities == 'TRANSFORMER':
-            av = self.mm_transformer(video, audio, key_padding_mask=key_padding_mask)
+            av = self.mm_transformer(video, audio, key_padding_mask=key_padding_mask, **kw)
         else:
             raise NotImplementedError("key_padding_mask with joint_modalities='NONE': its "
                                       "self-attention runs over the batch axis, where a mask "
