@@ -571,6 +571,51 @@ int jmt_head_bwd_drop(int h_dt, int gy_dt, int64_t rows, int hid, int k, const v
 int jmt_dropout_reference(const uint32_t ctr[4], int64_t rows, int64_t cols, int64_t split,
                           float p0, float p1, float* out);
 
+/* ------------------------------------------------------------------ attention dropout
+ * Dropout on the attention probabilities, O = dropout(softmax(S)) V (added to ABI 7, nothing else
+ * changes), with a counter-based mask of 8 bits per element whose unit is a block of 4 queries x
+ * 4 keys = the 16 bytes of one Philox4x32-10 call.  Element (nh, l, k): nh = n*H + h, query l,
+ * key k (absolute indices; key ranges do not shift them).  Key (seed_lo, seed_hi); counter
+ * (nh*QB + (l >> 2), k >> 2, call, stream) with QB = ceil(Lq / 4) and the state block of the
+ * regressor dropout (every attention forward takes a `call` of its own with jmt_dropout_next);
+ * N*H*QB <= 2^32, anything else is JMT_ERR_UNSUPPORTED.  The element's byte is byte k & 3 (bits
+ * 8 (k & 3) upward) of output word l & 3.  T8 = floor(256 p + 1/2) must be <= 255; an element is
+ * kept iff byte >= T8, so the rate in effect is p_eff = T8 / 256 (jmt_attn_dropout_rate(p); -1
+ * for a p outside [0, 1) or with T8 > 255); kept probabilities are multiplied by
+ * s = 1.0f / (1.0f - p_eff) in fp32.  T8 = 0 (p < 1 / 512): no mask, s = 1.
+ * jmt_attn_mh_fwd_drop / jmt_attn_mh_bwd_drop: jmt_attn_mh_fwd_kr / jmt_attn_mh_bwd_kr (kr ==
+ *   NULL: no ranges) + (p, ctr) before the stream, ctr a device uint32[4] written by
+ *   jmt_dropout_next.  With M = s * keep: o = (M o P) V and lse unchanged; dv = (M o P)^T dO,
+ *   dP = M o (dO V^T), dS = scale P o (dP - delta), delta = rowsum(dO o O) from the masked o.
+ *   The mask is regenerated in registers by all three kernels; nothing is stored per element.
+ *   T8 = 0 launches the plain kernels.  p outside [0, 1), T8 > 255, a null or misaligned ctr are
+ *   JMT_ERR_ARG.
+ * jmt_attn_dropout: y = M o x on an (NH*Lq, ld) buffer of f32 / bf16 / f16 whose row nh*Lq + l
+ *   holds the Lk keys of query l (the GEMM + softmax path's P and dP); in place (y == x, ldy ==
+ *   ldx; columns >= Lk stay as they are) or out of place (columns [Lk, ldy) are written as
+ *   zeros).  ldx, ldy multiples of 4 and >= 4 ceil(Lk / 4), rows 8-B aligned.
+ * jmt_attn_dropout_reference: host only, no GPU call: out[(nh*Lq + l)*Lk + k] = the multiplier
+ *   (0 or s) of element (nh, l, k) under the host array ctr, from the header the kernels
+ *   compile. */
+float jmt_attn_dropout_rate(float p);
+int jmt_attn_mh_fwd_drop(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                         int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l, int64_t sk_n,
+                         const void* v, int64_t sv_l, int64_t sv_n, void* o, int64_t so_l,
+                         int64_t so_n, float scale, float* lse, const int* kr, int kr_mod,
+                         float p, const uint32_t* ctr, void* stream);
+int jmt_attn_mh_bwd_drop(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                         int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l, int64_t so_n,
+                         const void* q, int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                         int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n,
+                         const float* lse, void* dq, int64_t sdq_l, int64_t sdq_n, void* dk,
+                         int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n,
+                         float scale, float* delta, const int* kr, int kr_mod, float p,
+                         const uint32_t* ctr, void* stream);
+int jmt_attn_dropout(int dt, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t NH,
+                     int64_t Lq, int64_t Lk, float p, const uint32_t* ctr, void* stream);
+int jmt_attn_dropout_reference(const uint32_t ctr[4], int64_t NH, int64_t Lq, int64_t Lk, float p,
+                               float* out);
+
 /* The head entries with a row map on y / gy (same ABI number: entry points added, none changed).
  * Memory row r of h (and of dh) pairs with row (r mod P) * Q + r div P of y_g / gy_g; P >= 1,
  * Q >= 1, P * Q = rows < 2^31, anything else is JMT_ERR_ARG.  P = rows, Q = 1 is the identity.

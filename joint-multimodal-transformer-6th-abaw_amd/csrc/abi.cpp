@@ -65,5 +65,36 @@ extern "C" int jmt_dropout_reference(const uint32_t ctr[4], int64_t rows, int64_
     }
   return JMT_OK;
 }
+extern "C" float jmt_attn_dropout_rate(float p) {
+  using namespace jmt;
+  if (!(p >= 0.f && p < 1.f)) return -1.f;
+  const uint32_t T8 = attn_dropout_threshold(p);
+  return T8 <= 255u ? attn_dropout_rate(T8) : -1.f;
+}
+extern "C" int jmt_attn_dropout_reference(const uint32_t ctr[4], int64_t NH, int64_t Lq,
+                                          int64_t Lk, float p, float* out) {
+  using namespace jmt;
+  if (!ctr || !out) return set_error(JMT_ERR_ARG, "jmt_attn_dropout_reference: null pointer");
+  if (NH < 0 || Lq < 0 || Lk < 0 || Lq >= ((int64_t)1 << 31) || Lk >= ((int64_t)1 << 31))
+    return set_error(JMT_ERR_ARG, "jmt_attn_dropout_reference: bad sizes (NH %lld Lq %lld Lk "
+                     "%lld)", (long long)NH, (long long)Lq, (long long)Lk);
+  if (!(p >= 0.f && p < 1.f))
+    return set_error(JMT_ERR_ARG, "jmt_attn_dropout_reference: rate must be in [0, 1)");
+  const uint32_t T8 = attn_dropout_threshold(p);
+  if (T8 > 255u)
+    return set_error(JMT_ERR_ARG, "jmt_attn_dropout_reference: rate %g rounds to T8 = %u > 255",
+                     (double)p, T8);
+  const uint32_t QB = attn_dropout_qblocks(Lq);
+  if (NH * (int64_t)QB > ((int64_t)1 << 32))
+    return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_dropout_reference: NH ceil(Lq / 4) exceeds "
+                     "the counter's 2^32 query blocks");
+  const float s = attn_dropout_scale(T8);
+  for (int64_t nh = 0; nh < NH; ++nh)
+    for (int64_t l = 0; l < Lq; ++l)
+      for (int64_t k = 0; k < Lk; ++k)
+        out[(nh * Lq + l) * Lk + k] =
+            attn_dropout_mult(ctr, QB, (uint32_t)nh, (uint32_t)l, (uint32_t)k, T8, s);
+  return JMT_OK;
+}
 // GEMM (3 dtypes x 4 layouts + split-K reduce) + row ops + CCC + SGD; informational only.
 extern "C" int jmt_kernel_count(void) { return 12 + 1 + 8 + 4 + 2 + 4; }

@@ -26,7 +26,12 @@
 // exponentiating -inf), are staged as zeros (their K / V rows are not read), and key tiles wholly
 // outside the range are skipped by the forward and the dQ kernel; the dK / dV kernel writes
 // exact zeros for them without a sweep.  The KR = false instantiations take AttnMhArgs alone.
+//
+// Attention dropout (DROP = true): the 8-bit counter-based mask of dropout.h, regenerated in
+// registers by all three kernels (one Philox call per lane and tile, shared by DPP within quads of
+// lanes; mh_drop_tile).  The DROP = false instantiations are the code of before.
 #include "attn_common.h"
+#include "dropout.h"
 
 namespace jmt {
 
@@ -52,6 +57,76 @@ struct AttnMhArgs {
 };
 
 typedef unsigned mh_u32x4 __attribute__((ext_vector_type(4)));
+
+// Attention dropout (DROP = true; the mask of dropout.h): the state copy of the call, the keep
+// threshold, QB = ceil(Lq / 4) and the scale of the kept probabilities.  Like the range table it
+// travels behind the kernel's arguments, so the DROP = false instantiations are the parent's.
+struct MhDrop {
+  const uint32_t* ctr;
+  uint32_t T8, QB;
+  float s;
+};
+template <typename A>
+struct WithDrop : A {
+  MhDrop dr;
+};
+template <bool KR, bool DROP>
+using MhArgs = std::conditional_t<DROP, WithDrop<KrArgs<AttnMhArgs, KR>>, KrArgs<AttnMhArgs, KR>>;
+
+// lane C of every quad of 4 adjacent lanes to the whole quad (DPP quad_perm, EXEC all ones)
+template <int C>
+__device__ __forceinline__ uint32_t mh_quad_bcast(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, C * 0x55, 0xf, 0xf, false);
+}
+// The mask bytes of a lane's 16 elements of one 64 x 64 tile: byte r of m[c] is the byte of
+// element (c, r).  The four lanes li = 4 a .. 4 a + 3 of equal g meet the same four 4 x 4 blocks
+// c = 0 .. 3: lane li & 3 = j makes the one Philox call of block c = j (the caller passes that
+// block's counter words), and the quad hands the words round.  QL (forward, dQ): the query on the
+// lane, keys 16 c + 4 g + r: the lane takes word l & 3 = li & 3 of every block, whose byte r is
+// key r's.  !QL (dK / dV): the key on the lane, queries 16 c + 4 g + r: the lane takes byte
+// k & 3 = li & 3 of word r.
+template <bool QL, int C>
+__device__ __forceinline__ uint32_t mh_drop_block(const Philox4& o, int j) {
+  const uint32_t w0 = mh_quad_bcast<C>(o.w[0]), w1 = mh_quad_bcast<C>(o.w[1]);
+  const uint32_t w2 = mh_quad_bcast<C>(o.w[2]), w3 = mh_quad_bcast<C>(o.w[3]);
+  if constexpr (QL) {
+    return j == 0 ? w0 : j == 1 ? w1 : j == 2 ? w2 : w3;
+  } else {
+    const int sh = 8 * j;
+    return ((w0 >> sh) & 255u) | (((w1 >> sh) & 255u) << 8) | (((w2 >> sh) & 255u) << 16) |
+           ((w3 >> sh) << 24);
+  }
+}
+template <bool QL>
+__device__ __forceinline__ void mh_drop_tile(const uint32_t (&ctr)[4], uint32_t qblk,
+                                             uint32_t kblk, int li, uint32_t (&m)[4]) {
+  uint32_t c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]};
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__OPTIMIZE__)
+  // The key is wave-uniform, so hipcc would keep all ten round keys of it in SGPRs across the
+  // tile loop (the dK / dV kernel then runs out of them).  Opaque here: they are re-derived per
+  // tile by a few scalar adds beside the vector work.
+  asm volatile("" : "+s"(c[0]), "+s"(c[1]));
+#endif
+  const Philox4 o = attn_dropout_block(c, qblk, kblk);
+  const int j = li & 3;
+  m[0] = mh_drop_block<QL, 0>(o, j);
+  m[1] = mh_drop_block<QL, 1>(o, j);
+  m[2] = mh_drop_block<QL, 2>(o, j);
+  m[3] = mh_drop_block<QL, 3>(o, j);
+}
+// All ones where element (c, r) of m = dm[c] is kept (byte >= T8, T8 >= 1), else 0; mh_masked
+// applies it to a value.  Plain vector arithmetic, opaque to the compiler: as compares, a tile's
+// sixteen keep bits take a pair of SGPRs each, more than the dK / dV kernel has to give.
+__device__ __forceinline__ uint32_t mh_keep(uint32_t m, int r, uint32_t T8) {
+  uint32_t k = (uint32_t)((int32_t)(T8 - 1u - ((m >> (8 * r)) & 255u)) >> 31);
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__OPTIMIZE__)
+  asm("" : "+v"(k));
+#endif
+  return k;
+}
+__device__ __forceinline__ float mh_masked(float x, uint32_t keep) {
+  return __uint_as_float(__float_as_uint(x) & keep);
+}
 
 // Byte offset of 16-B chunk ch of row `row` in a [64][DH] 16-bit image.  The XOR serves the row
 // reads (ds_read_b128: 16 rows, one chunk) and the transposed reads (a 32-lane half: 8 rows, one
@@ -125,8 +200,8 @@ __device__ __forceinline__ void mh_store_row(const f32x4 (&acc)[DH / 16], float 
   }
 }
 
-template <typename T, int DH, bool KR>
-__global__ __launch_bounds__(256, 2) void attn_mh_fwd_kernel(KrArgs<AttnMhArgs, KR> p) {
+template <typename T, int DH, bool KR, bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_mh_fwd_kernel(MhArgs<KR, DROP> p) {
   typedef typename Frag16<T>::t F;
   constexpr int NKS = DH / 32, NT = DH / 16, IMG = MH_ROWS * DH * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -159,6 +234,12 @@ __global__ __launch_bounds__(256, 2) void attn_mh_fwd_kernel(KrArgs<AttnMhArgs, 
   f32x4 o[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  uint32_t dctr[4] = {0u, 0u, 0u, 0u}, dqb = 0u;   // DROP: the state copy, the lane's query block
+  if constexpr (DROP) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dctr[i] = __builtin_amdgcn_readfirstlane(p.dr.ctr[i]);
+    dqb = (uint32_t)nh * p.dr.QB + (uint32_t)(qr >> 2);
+  }
 
   for (int kt = kt0; kt < kt1; ++kt) {
     __syncthreads();                               // the previous tile's reads are done
@@ -169,6 +250,10 @@ __global__ __launch_bounds__(256, 2) void attn_mh_fwd_kernel(KrArgs<AttnMhArgs, 
       mh_load<T, DH>(kreg, kb, p.sk_l, MH_ROWS * (kt + 1), kbeg, kend, p.Lk);
       mh_load<T, DH>(vreg, vb, p.sv_l, MH_ROWS * (kt + 1), kbeg, kend, p.Lk);
     }
+    // DROP: this lane's Philox call (key block 16 kt + 4 j + g, j = li & 3) beside the score MFMAs
+    uint32_t dm[4] = {0u, 0u, 0u, 0u};
+    if constexpr (DROP)
+      mh_drop_tile<true>(dctr, dqb, (uint32_t)(16 * kt + 4 * (li & 3) + g), li, dm);
     // s[c][r] = <query li, key 64 kt + 16 c + 4 g + r>
     f32x4 s[4];
 #pragma unroll
@@ -203,8 +288,10 @@ __global__ __launch_bounds__(256, 2) void attn_mh_fwd_kernel(KrArgs<AttnMhArgs, 
         const int key = MH_ROWS * kt + 16 * c + 4 * g + r;
         const bool in = key >= kbeg && key < kend;
         const float pv = in ? __builtin_amdgcn_exp2f(s[c][r] - mn) : 0.f;
-        l += pv;
-        pf[c >> 1][4 * (c & 1) + r] = from_f<T>(pv);
+        l += pv;                                   // the sum stays unmasked: lse is the plain one
+        if constexpr (DROP) pf[c >> 1][4 * (c & 1) + r] =
+            from_f<T>(mh_masked(pv, mh_keep(dm[c], r, p.dr.T8)));
+        else pf[c >> 1][4 * (c & 1) + r] = from_f<T>(pv);
       }
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc)
@@ -213,7 +300,8 @@ __global__ __launch_bounds__(256, 2) void attn_mh_fwd_kernel(KrArgs<AttnMhArgs, 
         o[t] = mfma16(mh_tr<T, DH>(vimg, 32 * cc, t, li, g), pf[cc], o[t]);
   }
   l = pl_pair_sum(l);
-  const float inv = l > 0.f ? 1.f / l : 0.f;       // an empty range: zeros
+  float inv = l > 0.f ? 1.f / l : 0.f;             // an empty range: zeros
+  if constexpr (DROP) inv *= p.dr.s;               // the kept probabilities' scale
   JMT_DCHECK(qr < p.Lq || qc == p.Lq - 1);
   mh_store_row<T, DH>(o, inv, (T*)p.out + (int64_t)n * p.so_n + hd * DH + (int64_t)qr * p.so_l, g,
                       qr < p.Lq);
@@ -221,8 +309,8 @@ __global__ __launch_bounds__(256, 2) void attn_mh_fwd_kernel(KrArgs<AttnMhArgs, 
     p.lse[(int64_t)nh * p.Lq + qr] = (m + __builtin_amdgcn_logf(l)) * 0.69314718055994531f;
 }
 
-template <typename T, int DH, bool KR>
-__global__ __launch_bounds__(256, 2) void attn_mh_dq_kernel(KrArgs<AttnMhArgs, KR> p) {
+template <typename T, int DH, bool KR, bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_mh_dq_kernel(MhArgs<KR, DROP> p) {
   typedef typename Frag16<T>::t F;
   constexpr int NKS = DH / 32, NT = DH / 16, IMG = MH_ROWS * DH * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -266,6 +354,12 @@ __global__ __launch_bounds__(256, 2) void attn_mh_dq_kernel(KrArgs<AttnMhArgs, K
   f32x4 acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  uint32_t dctr[4] = {0u, 0u, 0u, 0u}, dqb = 0u;   // DROP: as the forward
+  if constexpr (DROP) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dctr[i] = __builtin_amdgcn_readfirstlane(p.dr.ctr[i]);
+    dqb = (uint32_t)nh * p.dr.QB + (uint32_t)(qr >> 2);
+  }
 
   for (int kt = kt0; kt < kt1; ++kt) {
     __syncthreads();
@@ -276,6 +370,9 @@ __global__ __launch_bounds__(256, 2) void attn_mh_dq_kernel(KrArgs<AttnMhArgs, K
       mh_load<T, DH>(kreg, kb, p.sk_l, MH_ROWS * (kt + 1), kbeg, kend, p.Lk);
       mh_load<T, DH>(vreg, vb, p.sv_l, MH_ROWS * (kt + 1), kbeg, kend, p.Lk);
     }
+    uint32_t dm[4] = {0u, 0u, 0u, 0u};
+    if constexpr (DROP)
+      mh_drop_tile<true>(dctr, dqb, (uint32_t)(16 * kt + 4 * (li & 3) + g), li, dm);
     F dsf[2];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -290,7 +387,9 @@ __global__ __launch_bounds__(256, 2) void attn_mh_dq_kernel(KrArgs<AttnMhArgs, K
         const int key = MH_ROWS * kt + 16 * c + 4 * g + r;
         const bool in = key >= kbeg && key < kend;
         const float pv = in ? __builtin_amdgcn_exp2f(s[r] * p.scale_log2 - lse2) : 0.f;
-        dsf[c >> 1][4 * (c & 1) + r] = from_f<T>(in ? p.scale * pv * (d[r] - delta) : 0.f);
+        float dp = d[r];
+        if constexpr (DROP) dp = mh_masked(dp * p.dr.s, mh_keep(dm[c], r, p.dr.T8));  // M o dO V^T
+        dsf[c >> 1][4 * (c & 1) + r] = from_f<T>(in ? p.scale * pv * (dp - delta) : 0.f);
       }
     }
 #pragma unroll
@@ -306,8 +405,8 @@ __global__ __launch_bounds__(256, 2) void attn_mh_dq_kernel(KrArgs<AttnMhArgs, K
   if (qr < p.Lq && g == 0) p.delta[(int64_t)nh * p.Lq + qr] = delta;
 }
 
-template <typename T, int DH, bool KR>
-__global__ __launch_bounds__(256, 2) void attn_mh_dkdv_kernel(KrArgs<AttnMhArgs, KR> p) {
+template <typename T, int DH, bool KR, bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_mh_dkdv_kernel(MhArgs<KR, DROP> p) {
   typedef typename Frag16<T>::t F;
   constexpr int NKS = DH / 32, NT = DH / 16, IMG = MH_ROWS * DH * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -363,6 +462,12 @@ __global__ __launch_bounds__(256, 2) void attn_mh_dkdv_kernel(KrArgs<AttnMhArgs,
   mh_load<T, DH>(qreg, qb, p.sq_l, 0, 0, p.Lq, p.Lq);
   mh_load<T, DH>(greg, gb, p.sgo_l, 0, 0, p.Lq, p.Lq);
   load_consts(0);
+  uint32_t dctr[4] = {0u, 0u, 0u, 0u}, dqb = 0u;   // DROP: the state copy, query block 4 j + g
+  if constexpr (DROP) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dctr[i] = __builtin_amdgcn_readfirstlane(p.dr.ctr[i]);
+    dqb = (uint32_t)nh * p.dr.QB + (uint32_t)(4 * (li & 3) + g);
+  }
 
   for (int qt = 0; qt < nqt; ++qt) {
     __syncthreads();
@@ -375,6 +480,10 @@ __global__ __launch_bounds__(256, 2) void attn_mh_dkdv_kernel(KrArgs<AttnMhArgs,
       mh_load<T, DH>(greg, gb, p.sgo_l, MH_ROWS * (qt + 1), 0, p.Lq, p.Lq);
       load_consts(MH_ROWS * (qt + 1));
     }
+    // DROP: this lane's Philox call is query block 16 qt + 4 j + g (j = li & 3) of its key block
+    uint32_t dm[4] = {0u, 0u, 0u, 0u};
+    if constexpr (DROP)
+      mh_drop_tile<false>(dctr, dqb + (uint32_t)(16 * qt), (uint32_t)(kr >> 2), li, dm);
     // s[r] = <query 64 qt + 16 c + 4 g + r, key kr>: the key on the lane
     F pf[2], dsf[2];
 #pragma unroll
@@ -392,8 +501,17 @@ __global__ __launch_bounds__(256, 2) void attn_mh_dkdv_kernel(KrArgs<AttnMhArgs,
         const int qi = MH_ROWS * qt + 16 * c + 4 * g + r;
         const bool in = kin && qi < p.Lq;
         const float pv = in ? __builtin_amdgcn_exp2f(s[r] * p.scale_log2 - l4[r]) : 0.f;
-        pf[c >> 1][4 * (c & 1) + r] = from_f<T>(pv);
-        dsf[c >> 1][4 * (c & 1) + r] = from_f<T>(in ? p.scale * pv * (d[r] - d4[r]) : 0.f);
+        float dp = d[r];
+        if constexpr (DROP) {
+          // dV takes the masked P (its scale s waits for the store), dS the masked dP and the
+          // plain P
+          const uint32_t keep = mh_keep(dm[c], r, p.dr.T8);
+          pf[c >> 1][4 * (c & 1) + r] = from_f<T>(mh_masked(pv, keep));
+          dp = mh_masked(dp * p.dr.s, keep);
+        } else {
+          pf[c >> 1][4 * (c & 1) + r] = from_f<T>(pv);
+        }
+        dsf[c >> 1][4 * (c & 1) + r] = from_f<T>(in ? p.scale * pv * (dp - d4[r]) : 0.f);
       }
     }
 #pragma unroll
@@ -407,7 +525,9 @@ __global__ __launch_bounds__(256, 2) void attn_mh_dkdv_kernel(KrArgs<AttnMhArgs,
   // keys of this tile outside the range: exact zeros (the buffers arrive uninitialised)
   JMT_DCHECK(kr < p.Lk || kc == p.Lk - 1);
   mh_store_row<T, DH>(dk, kin ? 1.f : 0.f, dkrow, g, kr < p.Lk);
-  mh_store_row<T, DH>(dv, kin ? 1.f : 0.f, dvrow, g, kr < p.Lk);
+  float vmul = 1.f;
+  if constexpr (DROP) vmul = p.dr.s;
+  mh_store_row<T, DH>(dv, kin ? vmul : 0.f, dvrow, g, kr < p.Lk);
 }
 
 static int64_t mh_tiles(int L) { return ((int64_t)L + MH_ROWS - 1) / MH_ROWS; }
@@ -424,21 +544,25 @@ static int mh_check(const char* name, int N, int H, const void* const* ptrs, int
   return JMT_OK;
 }
 
-// launch K<T, DH, KR> for the runtime (dt, dh, kr) on ntile-tile items
-#define MH_LAUNCH(KERNEL, LDS_OF, a, kr, dt, dh, grid, st)                                     \
+// launch K<T, DH, KR, DROP> for the runtime (dt, dh, kr, dr) on ntile-tile items
+#define MH_LAUNCH(KERNEL, LDS_OF, a, kr, dr, dt, dh, grid, st)                                 \
   by_elem(dt, [&](auto e) {                                                                    \
     using T = typename decltype(e)::type;                                                      \
     auto go = [&](auto dhc) {                                                                  \
       constexpr int DH = decltype(dhc)::value;                                                 \
       constexpr int LDS = LDS_OF(DH);                                                          \
-      if (kr) {                                                                                \
-        WithKeyRange<AttnMhArgs> ak;                                                           \
+      auto run = [&](auto krc, auto drc) {                                                     \
+        constexpr bool KR = decltype(krc)::value, DROP = decltype(drc)::value;                 \
+        MhArgs<KR, DROP> ak;                                                                   \
         static_cast<AttnMhArgs&>(ak) = a;                                                      \
-        ak.kr = *kr;                                                                           \
-        attn_launch<KERNEL<T, DH, true>, LDS, 256>(grid, st, ak);                              \
-      } else {                                                                                 \
-        attn_launch<KERNEL<T, DH, false>, LDS, 256>(grid, st, a);                              \
-      }                                                                                        \
+        if constexpr (KR) ak.kr = *kr;                                                         \
+        if constexpr (DROP) ak.dr = *dr;                                                       \
+        attn_launch<KERNEL<T, DH, KR, DROP>, LDS, 256>(grid, st, ak);                          \
+      };                                                                                       \
+      if (kr && dr) run(std::true_type{}, std::true_type{});                                   \
+      else if (dr) run(std::false_type{}, std::true_type{});                                   \
+      else if (kr) run(std::true_type{}, std::false_type{});                                   \
+      else run(std::false_type{}, std::false_type{});                                          \
     };                                                                                         \
     if (dh == 64) go(std::integral_constant<int, 64>{});                                       \
     else go(std::integral_constant<int, 128>{});                                               \
@@ -465,6 +589,27 @@ static int mh_unsupported(const char* name, int dt, int dh, int N, int H, int Lq
                    "jmt_attn_mh_ok", name, dt, dh, N, H, Lq, Lk);
 }
 
+// The checks of the *_drop entry points on (p, ctr) and the counter limit N H QB <= 2^32; fills
+// `d`.  d->T8 == 0 (p < 1 / 512): no mask, the caller launches the plain kernels.
+static int mh_drop_check(const char* name, int N, int H, int Lq, float p, const uint32_t* ctr,
+                         MhDrop* d) {
+  JMT_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout rate %g outside [0, 1)", name, (double)p);
+  const uint32_t T8 = attn_dropout_threshold(p);
+  JMT_CHECK_ARG(T8 <= 255u, "%s: dropout rate %g rounds to T8 = %u > 255 (the rate is quantised "
+                "to 1 / 256)", name, (double)p, T8);
+  JMT_CHECK_ARG(ctr != nullptr && ((uintptr_t)ctr & 3) == 0,
+                "%s: dropout counter block null or not 4-B aligned", name);
+  const uint32_t QB = attn_dropout_qblocks(Lq);
+  if ((int64_t)N * H * QB > ((int64_t)1 << 32))
+    return set_error(JMT_ERR_UNSUPPORTED, "%s: N %d H %d Lq %d: N H ceil(Lq / 4) exceeds the "
+                     "dropout counter's 2^32 query blocks", name, N, H, Lq);
+  d->ctr = ctr;
+  d->T8 = T8;
+  d->QB = QB;
+  d->s = attn_dropout_scale(T8);
+  return JMT_OK;
+}
+
 static void mh_fill(AttnMhArgs& a, int H, int Lq, int Lk, float scale) {
   a.H = H;
   a.Lq = Lq;
@@ -478,7 +623,7 @@ static int mh_fwd_impl(const char* name, int dt, int N, int H, int Lq, int Lk, i
                        const void* q, int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
                        int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n, void* o,
                        int64_t so_l, int64_t so_n, float scale, float* lse, const KeyRange* kr,
-                       void* stream) {
+                       const MhDrop* dr, void* stream) {
   if (N == 0 || Lq == 0) return JMT_OK;
   if (!jmt_attn_mh_ok(dt, dh, N, H, Lq, Lk, sq_l, sk_l, sv_l))
     return mh_unsupported(name, dt, dh, N, H, Lq, Lk);
@@ -495,7 +640,7 @@ static int mh_fwd_impl(const char* name, int dt, int N, int H, int Lq, int Lk, i
   a.ntile = (int)mh_tiles(Lq);
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)((int64_t)N * H * a.ntile));
-  MH_LAUNCH(attn_mh_fwd_kernel, MH_LDS2, a, kr, dt, dh, grid, st);
+  MH_LAUNCH(attn_mh_fwd_kernel, MH_LDS2, a, kr, dr, dt, dh, grid, st);
   JMT_LAUNCH_CHECK(name);
   return JMT_OK;
 }
@@ -506,7 +651,7 @@ extern "C" int jmt_attn_mh_fwd(int dt, int N, int H, int Lq, int Lk, int dh, con
                                int64_t so_l, int64_t so_n, float scale, float* lse,
                                void* stream) {
   return mh_fwd_impl("jmt_attn_mh_fwd", dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v,
-                     sv_l, sv_n, o, so_l, so_n, scale, lse, nullptr, stream);
+                     sv_l, sv_n, o, so_l, so_n, scale, lse, nullptr, nullptr, stream);
 }
 
 extern "C" int jmt_attn_mh_fwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
@@ -516,7 +661,7 @@ extern "C" int jmt_attn_mh_fwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, 
                                   const int* kr, int kr_mod, void* stream) {
   const KeyRange r = {kr, kr_mod};
   return mh_fwd_impl("jmt_attn_mh_fwd_kr", dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v,
-                     sv_l, sv_n, o, so_l, so_n, scale, lse, &r, stream);
+                     sv_l, sv_n, o, so_l, so_n, scale, lse, &r, nullptr, stream);
 }
 
 // jmt_attn_mh_bwd (kr == NULL) and jmt_attn_mh_bwd_kr: the dQ kernel, then the dK / dV kernel
@@ -526,7 +671,8 @@ static int mh_bwd_impl(const char* name, int dt, int N, int H, int Lq, int Lk, i
                        int64_t sk_l, int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n,
                        const float* lse, void* dq, int64_t sdq_l, int64_t sdq_n, void* dk,
                        int64_t sdk_l, int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n,
-                       float scale, float* delta, const KeyRange* kr, void* stream) {
+                       float scale, float* delta, const KeyRange* kr, const MhDrop* dr,
+                       void* stream) {
   if (N == 0 || Lq == 0) return JMT_OK;
   if (!jmt_attn_mh_ok(dt, dh, N, H, Lq, Lk, sq_l, sk_l, sv_l))
     return mh_unsupported(name, dt, dh, N, H, Lq, Lk);
@@ -552,13 +698,13 @@ static int mh_bwd_impl(const char* name, int dt, int N, int H, int Lq, int Lk, i
   {
     a.ntile = (int)mh_tiles(Lq);
     const dim3 grid((unsigned)((int64_t)N * H * a.ntile));
-    MH_LAUNCH(attn_mh_dq_kernel, MH_LDS2, a, kr, dt, dh, grid, st);
+    MH_LAUNCH(attn_mh_dq_kernel, MH_LDS2, a, kr, dr, dt, dh, grid, st);
     JMT_LAUNCH_CHECK(name);
   }
   {
     a.ntile = (int)mh_tiles(Lk);
     const dim3 grid((unsigned)((int64_t)N * H * a.ntile));
-    MH_LAUNCH(attn_mh_dkdv_kernel, MH_LDS2C, a, kr, dt, dh, grid, st);
+    MH_LAUNCH(attn_mh_dkdv_kernel, MH_LDS2C, a, kr, dr, dt, dh, grid, st);
     JMT_LAUNCH_CHECK(name);
   }
   return JMT_OK;
@@ -574,7 +720,7 @@ extern "C" int jmt_attn_mh_bwd(int dt, int N, int H, int Lq, int Lk, int dh, con
                                float* delta, void* stream) {
   return mh_bwd_impl("jmt_attn_mh_bwd", dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q,
                      sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, lse, dq, sdq_l, sdq_n, dk, sdk_l,
-                     sdk_n, dv, sdv_l, sdv_n, scale, delta, nullptr, stream);
+                     sdk_n, dv, sdv_l, sdv_n, scale, delta, nullptr, nullptr, stream);
 }
 
 extern "C" int jmt_attn_mh_bwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
@@ -589,5 +735,47 @@ extern "C" int jmt_attn_mh_bwd_kr(int dt, int N, int H, int Lq, int Lk, int dh, 
   const KeyRange r = {kr, kr_mod};
   return mh_bwd_impl("jmt_attn_mh_bwd_kr", dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n,
                      q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, lse, dq, sdq_l, sdq_n, dk,
-                     sdk_l, sdk_n, dv, sdv_l, sdv_n, scale, delta, &r, stream);
+                     sdk_l, sdk_n, dv, sdv_l, sdv_n, scale, delta, &r, nullptr, stream);
+}
+
+// jmt_attn_mh_fwd_drop / jmt_attn_mh_bwd_drop: attention dropout on the probabilities (the mask
+// of dropout.h), with or without a range table (kr == NULL: none).  T8 == 0: the plain kernels.
+extern "C" int jmt_attn_mh_fwd_drop(int dt, int N, int H, int Lq, int Lk, int dh, const void* q,
+                                    int64_t sq_l, int64_t sq_n, const void* k, int64_t sk_l,
+                                    int64_t sk_n, const void* v, int64_t sv_l, int64_t sv_n,
+                                    void* o, int64_t so_l, int64_t so_n, float scale, float* lse,
+                                    const int* kr, int kr_mod, float p, const uint32_t* ctr,
+                                    void* stream) {
+  const char* name = "jmt_attn_mh_fwd_drop";
+  if (N == 0 || Lq == 0) return JMT_OK;
+  if (!jmt_attn_mh_ok(dt, dh, N, H, Lq, Lk, sq_l, sk_l, sv_l))
+    return mh_unsupported(name, dt, dh, N, H, Lq, Lk);
+  MhDrop d = {};
+  const int rc = mh_drop_check(name, N, H, Lq, p, ctr, &d);
+  if (rc != JMT_OK) return rc;
+  const KeyRange r = {kr, kr_mod};
+  return mh_fwd_impl(name, dt, N, H, Lq, Lk, dh, q, sq_l, sq_n, k, sk_l, sk_n, v, sv_l, sv_n, o,
+                     so_l, so_n, scale, lse, kr ? &r : nullptr, d.T8 ? &d : nullptr, stream);
+}
+
+extern "C" int jmt_attn_mh_bwd_drop(int dt, int N, int H, int Lq, int Lk, int dh, const void* go,
+                                    int64_t sgo_l, int64_t sgo_n, const void* o, int64_t so_l,
+                                    int64_t so_n, const void* q, int64_t sq_l, int64_t sq_n,
+                                    const void* k, int64_t sk_l, int64_t sk_n, const void* v,
+                                    int64_t sv_l, int64_t sv_n, const float* lse, void* dq,
+                                    int64_t sdq_l, int64_t sdq_n, void* dk, int64_t sdk_l,
+                                    int64_t sdk_n, void* dv, int64_t sdv_l, int64_t sdv_n,
+                                    float scale, float* delta, const int* kr, int kr_mod, float p,
+                                    const uint32_t* ctr, void* stream) {
+  const char* name = "jmt_attn_mh_bwd_drop";
+  if (N == 0 || Lq == 0) return JMT_OK;
+  if (!jmt_attn_mh_ok(dt, dh, N, H, Lq, Lk, sq_l, sk_l, sv_l))
+    return mh_unsupported(name, dt, dh, N, H, Lq, Lk);
+  MhDrop d = {};
+  const int rc = mh_drop_check(name, N, H, Lq, p, ctr, &d);
+  if (rc != JMT_OK) return rc;
+  const KeyRange r = {kr, kr_mod};
+  return mh_bwd_impl(name, dt, N, H, Lq, Lk, dh, go, sgo_l, sgo_n, o, so_l, so_n, q, sq_l, sq_n, k,
+                     sk_l, sk_n, v, sv_l, sv_n, lse, dq, sdq_l, sdq_n, dk, sdk_l, sdk_n, dv, sdv_l,
+                     sdv_n, scale, delta, kr ? &r : nullptr, d.T8 ? &d : nullptr, stream);
 }

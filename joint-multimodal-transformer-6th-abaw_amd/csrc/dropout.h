@@ -65,4 +65,37 @@ JMT_HD void dropout_quad(const uint32_t* ctr, uint32_t row, uint32_t quad, uint3
   for (int i = 0; i < 4; ++i) m[i] = o.w[i] >= T ? s : 0.f;
 }
 
+// The attention dropout mask: one specification for the fused multi-head kernels
+// (attn_mh.hip), the GEMM + softmax path (dropout.hip jmt_attn_dropout) and the host reference
+// (abi.cpp jmt_attn_dropout_reference).  8 bits per element; the unit is a block of 4 queries x
+// 4 keys = the 16 bytes of one Philox4x32-10 call.
+//
+//   element    (nh, l, k): nh = n H + h, query l, key k (absolute indices)
+//   key        (seed_lo, seed_hi)                       } the regressors' state block, a `call`
+//   counter    (nh QB + (l >> 2), k >> 2, call, stream) } of its own per attention forward
+//              QB = ceil(Lq / 4); N H QB <= 2^32
+//   byte       byte k & 3 (bits 8 (k & 3) upward) of output word l & 3
+//   keep       byte >= T8, T8 = floor(256 p + 1/2) <= 255: the rate is quantised to
+//              p_eff = T8 / 256; T8 = 0: no mask
+//   scale      kept probabilities are multiplied by s = 1.0f / (1.0f - p_eff), dropped ones by 0
+JMT_HD uint32_t attn_dropout_threshold(float p) { return (uint32_t)(256.0 * (double)p + 0.5); }
+JMT_HD float attn_dropout_rate(uint32_t T8) { return (float)T8 / 256.0f; }
+JMT_HD float attn_dropout_scale(uint32_t T8) { return 1.0f / (1.0f - attn_dropout_rate(T8)); }
+JMT_HD uint32_t attn_dropout_qblocks(int64_t Lq) { return (uint32_t)((Lq + 3) / 4); }
+
+// the 16 bytes of block (qblk, kblk), qblk = nh QB + (l >> 2), kblk = k >> 2
+JMT_HD Philox4 attn_dropout_block(const uint32_t* ctr, uint32_t qblk, uint32_t kblk) {
+  return philox4x32_10(qblk, kblk, ctr[2], ctr[3], ctr[0], ctr[1]);
+}
+// the byte of query l, key k in its block's words
+JMT_HD uint32_t attn_dropout_byte(const Philox4& o, uint32_t l, uint32_t k) {
+  return (o.w[l & 3u] >> (8u * (k & 3u))) & 255u;
+}
+// the multiplier (0 or s) of element (nh, l, k)
+JMT_HD float attn_dropout_mult(const uint32_t* ctr, uint32_t QB, uint32_t nh, uint32_t l,
+                               uint32_t k, uint32_t T8, float s) {
+  const Philox4 o = attn_dropout_block(ctr, nh * QB + (l >> 2), k >> 2);
+  return attn_dropout_byte(o, l, k) >= T8 ? s : 0.f;
+}
+
 }  // namespace jmt

@@ -5,6 +5,8 @@
 //   jmt_dropout       y = m . x over a (rows x cols) block, in place or not: the regressors'
 //                     hidden activations on the GEMM route (functional.MLPFn / MLPPairFn), once
 //                     on h after the ReLU GEMM and once on dh after the masked dgrad
+//   jmt_attn_dropout  the attention mask (8 bits per element, 4 x 4 blocks) on the GEMM + softmax
+//                     path's probabilities and on its dP
 // A lane owns one quad (4 consecutive columns = one Philox call): one 8-B access for the 16-bit
 // types, two for fp32; the product is formed in fp32 and rounded once.
 #include "common.h"
@@ -89,9 +91,95 @@ __global__ __launch_bounds__(256) void dropout_kernel(DropArgs a) {
   Quad<T>::st((T*)a.y + r * a.ldy + 4 * q, v);
 }
 
+// The attention mask (dropout.h) on a materialised (NH Lq, ld) buffer: the GEMM + softmax path's
+// probabilities (out of place: P~ for the P V and dV GEMMs) and its fp32 dP (in place).  A lane
+// owns 4 consecutive keys of one row = one word of the block's Philox call.
+struct AttnDropArgs {
+  const void* x;
+  void* y;
+  int64_t ldx, ldy, rows;    // rows = NH Lq
+  int Lq, Lk, quads;         // quads per row: ceil(Lk / 4) in place, ldy / 4 out of place
+  uint32_t T8, QB;
+  float s;
+  const uint32_t* ctr;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_dropout_kernel(AttnDropArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = i / a.quads;
+  if (row >= a.rows) return;
+  const int q = (int)(i - row * a.quads);
+  const bool inplace = a.x == a.y;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  JMT_DCHECK(4 * q + 3 < a.ldy);
+  if (4 * q < a.Lk) {
+    const uint32_t ctr[4] = {a.ctr[0], a.ctr[1], a.ctr[2], a.ctr[3]};
+    const uint32_t nh = (uint32_t)(row / a.Lq), l = (uint32_t)(row - (int64_t)nh * a.Lq);
+    const Philox4 o = attn_dropout_block(ctr, nh * a.QB + (l >> 2), (uint32_t)q);
+    JMT_DCHECK(4 * q + 3 < a.ldx);
+    Quad<T>::ld((const T*)a.x + row * a.ldx + 4 * q, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (4 * q + e < a.Lk) v[e] *= attn_dropout_byte(o, l, (uint32_t)e) >= a.T8 ? a.s : 0.f;
+      else if (!inplace) v[e] = 0.f;               // padding columns: zeros out of place
+    }
+  }
+  Quad<T>::st((T*)a.y + row * a.ldy + 4 * q, v);
+}
+
 }  // namespace jmt
 
 using namespace jmt;
+
+extern "C" int jmt_attn_dropout(int dt, const void* x, int64_t ldx, void* y, int64_t ldy,
+                                int64_t NH, int64_t Lq, int64_t Lk, float p, const uint32_t* ctr,
+                                void* stream) {
+  JMT_CHECK_ARG(dt == JMT_F32 || dt == JMT_BF16 || dt == JMT_F16, "jmt_attn_dropout: dtype %d",
+                dt);
+  JMT_CHECK_ARG(x && y, "jmt_attn_dropout: null pointer");
+  JMT_CHECK_ARG(ctr != nullptr && ((uintptr_t)ctr & 3) == 0,
+                "jmt_attn_dropout: counter block null or not 4-B aligned");
+  JMT_CHECK_ARG(NH >= 0 && Lq >= 0 && Lk >= 0 && Lq < ((int64_t)1 << 31) &&
+                    Lk < ((int64_t)1 << 31) - 4,
+                "jmt_attn_dropout: bad sizes (NH %lld Lq %lld Lk %lld)", (long long)NH,
+                (long long)Lq, (long long)Lk);
+  JMT_CHECK_ARG(p >= 0.f && p < 1.f, "jmt_attn_dropout: rate %g outside [0, 1)", (double)p);
+  const uint32_t T8 = attn_dropout_threshold(p);
+  JMT_CHECK_ARG(T8 <= 255u, "jmt_attn_dropout: rate %g rounds to T8 = %u > 255", (double)p, T8);
+  const int64_t lkq = 4 * ((Lk + 3) / 4);
+  const int es = dtype_size(dt);
+  JMT_CHECK_ARG(ldx >= lkq && ldy >= lkq && ldx % 4 == 0 && ldy % 4 == 0 &&
+                    ldy < ((int64_t)1 << 31),
+                "jmt_attn_dropout: row strides must be multiples of 4 and hold ceil(Lk / 4) quads");
+  JMT_CHECK_ARG(((uintptr_t)x & 7) == 0 && ((uintptr_t)y & 7) == 0 && (ldx * es) % 8 == 0 &&
+                    (ldy * es) % 8 == 0,
+                "jmt_attn_dropout: x / y rows not 8-B aligned");
+  JMT_CHECK_ARG(x != y || ldx == ldy, "jmt_attn_dropout: in place with two row strides");
+  const uint32_t QB = attn_dropout_qblocks(Lq);
+  if (NH * (int64_t)QB > ((int64_t)1 << 32))
+    return set_error(JMT_ERR_UNSUPPORTED, "jmt_attn_dropout: NH %lld Lq %lld: NH ceil(Lq / 4) "
+                     "exceeds the dropout counter's 2^32 query blocks", (long long)NH,
+                     (long long)Lq);
+  if (NH == 0 || Lq == 0 || Lk == 0) return JMT_OK;
+  AttnDropArgs a = {};
+  a.x = x; a.y = y; a.ldx = ldx; a.ldy = ldy; a.rows = NH * Lq;
+  a.Lq = (int)Lq; a.Lk = (int)Lk;
+  a.quads = (int)(x == y ? lkq / 4 : ldy / 4);
+  a.T8 = T8; a.QB = QB; a.s = attn_dropout_scale(T8);
+  a.ctr = ctr;
+  const int64_t nblk = (a.rows * a.quads + 255) / 256;
+  JMT_CHECK_ARG(nblk < ((int64_t)1 << 31), "jmt_attn_dropout: %lld x %lld exceeds one launch",
+                (long long)a.rows, (long long)Lk);
+  const dim3 grid((unsigned)nblk);
+  hipStream_t st = as_stream(stream);
+  if (dt == JMT_F32) hipLaunchKernelGGL(attn_dropout_kernel<float>, grid, dim3(256), 0, st, a);
+  else if (dt == JMT_BF16)
+    hipLaunchKernelGGL(attn_dropout_kernel<__bf16>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(attn_dropout_kernel<_Float16>, grid, dim3(256), 0, st, a);
+  JMT_LAUNCH_CHECK("jmt_attn_dropout");
+  return JMT_OK;
+}
 
 extern "C" int jmt_dropout_next(uint32_t* state, uint32_t* out, void* stream) {
   JMT_CHECK_ARG(state, "jmt_dropout_next: null state");

@@ -220,6 +220,22 @@ _PROTOS = {
                                   c_f, c_f, c_vp, c_vp]),
     "jmt_dropout_reference": (c_int, [C.POINTER(C.c_uint32), c_i64, c_i64, c_i64, c_f, c_f,
                                       c_fp]),
+    # attention dropout (csrc/dropout.h): the *_drop attention entries are jmt_attn_mh_fwd_kr /
+    # jmt_attn_mh_bwd_kr + (p, ctr) before the stream (kr may be NULL);
+    # jmt_attn_dropout(dt, x, ldx, y, ldy, NH, Lq, Lk, p, ctr, stream); the reference is host only
+    "jmt_attn_dropout_rate": (c_f, [c_f]),
+    "jmt_attn_mh_fwd_drop": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                     c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                     c_i64, c_f, c_vp, c_vp, c_int, c_f, c_vp, c_vp]),
+    "jmt_attn_mh_bwd_drop": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                     c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                     c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
+                                     c_i64, c_i64, c_vp, c_i64, c_i64, c_f, c_vp, c_vp, c_int,
+                                     c_f, c_vp, c_vp]),
+    "jmt_attn_dropout": (c_int, [c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_f, c_vp,
+                                 c_vp]),
+    "jmt_attn_dropout_reference": (c_int, [C.POINTER(C.c_uint32), c_i64, c_i64, c_i64, c_f,
+                                           c_fp]),
     "jmt_ce_stats": (c_int, [c_int, c_i64, c_int, c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp]),
     "jmt_ce_finish": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp]),
     "jmt_ce_bwd": (c_int, [c_int, c_i64, c_int, c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp, c_vp,

@@ -93,13 +93,20 @@ def override(cfg: dict, argv: Sequence[str]) -> dict:
 
 
 def fusion_model(cfg: dict, vision_in_ft: int = 512, **kw):
-    """main.py:473-481."""
+    """main.py:473-481.  An optional `attn_dropout` (not in the reference's file) sets dropout
+    on the attention probabilities of every attention module (jmt.nn.set_attention_dropout);
+    absent means 0."""
     from models.two_transformers import Two_transformers
+    from .nn import set_attention_dropout
     mp = cfg["model_params"]
-    return Two_transformers(v_dropout=float(mp["v_dropout"]), a_dropout=float(mp["a_dropout"]),
-                            num_heads=int(mp["num_heads"]), num_layers=int(mp["num_layers"]),
-                            joint_modalities=mp["joint_modalities"],
-                            output_format=mp["output_format"], vision_in_ft=vision_in_ft, **kw)
+    model = Two_transformers(v_dropout=float(mp["v_dropout"]), a_dropout=float(mp["a_dropout"]),
+                             num_heads=int(mp["num_heads"]), num_layers=int(mp["num_layers"]),
+                             joint_modalities=mp["joint_modalities"],
+                             output_format=mp["output_format"], vision_in_ft=vision_in_ft, **kw)
+    p = float(mp.get("attn_dropout") or 0.0)
+    if p != 0.0:
+        set_attention_dropout(model, p)
+    return model
 
 
 def sgd_kwargs(cfg: dict) -> Dict[str, float]:

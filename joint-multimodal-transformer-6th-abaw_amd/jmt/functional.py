@@ -924,8 +924,9 @@ class AttnCoreFn(Function):
         return P
 
     @staticmethod
-    def forward(ctx, q_src, k_src, v_src, E, H, qcol, kcol, vcol, kr=None):
-        o, saved = attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, kr=kr)
+    def forward(ctx, q_src, k_src, v_src, E, H, qcol, kcol, vcol, kr=None, drop_p=0.0):
+        o, saved = attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, kr=kr,
+                                drop_p=drop_p)
         # which inputs are the same tensor (saved tensors are not guaranteed to unpack to the
         # same Python objects, so the aliasing is recorded here)
         owner = (0, 0 if k_src is q_src else 1,
@@ -958,7 +959,7 @@ class AttnCoreFn(Function):
                     bufs[i].zero_()
         attn_backward((tensors, meta), go, bufs[owner[0]], bufs[owner[1]], bufs[owner[2]])
         grads = [bufs[i] if owner[i] == i else None for i in range(3)]
-        return (*grads, None, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None, None)
 
 
 def _small_aligned(t, col, cd):
@@ -998,18 +999,35 @@ class AttnPlan(NamedTuple):
 
 # what attn_backward keeps of an attn_forward call besides its tensors (fwd: AttnPlan.fwd)
 # kr: the key range operand (table, kr_mod) of a call with ranges, else None
-AttnMeta = collections.namedtuple("AttnMeta", "E H qcol kcol vcol ldS scale cd fwd kr")
+# drop: (p, state copy) of a call with attention dropout (the operand of the ops wrappers), else
+# None
+AttnMeta = collections.namedtuple("AttnMeta", "E H qcol kcol vcol ldS scale cd fwd kr drop",
+                                  defaults=(None,))
+
+
+def attn_dropout_rate(p) -> float:
+    """The attention dropout rate in effect for `p`.  The mask spends 8 bits per element
+    (csrc/dropout.h), so the rate is quantised to 1 / 256: p_eff = floor(256 p + 1/2) / 256, and
+    kept probabilities are scaled by 1 / (1 - p_eff).  p < 1 / 512 is no dropout at all."""
+    return ops.attn_dropout_rate(_check_rate(p))
+
+
+def _attn_drop_counter_ok(N, H, Lq) -> bool:
+    """The mask's counter holds 32 bits of (sequence, head, 4-query block)."""
+    return N * H * ((Lq + 3) // 4) <= 1 << 32
 
 
 def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=None,
-              fwd=None, kr=False) -> AttnPlan:
+              fwd=None, kr=False, drop=False) -> AttnPlan:
     """The one place an attention call's kernels are chosen (host only, no tensors).  q .. dv:
     AttnOperand of each view, the gradient ones (go: dO as attn_backward normalises it) once they
     exist.  fwd: the forward path already taken (attn_backward; the saved state fixes it).  The
     switches (ops._attn_fused / _attn_short / _attn_mh / _attn_dkdv / _attn_pds, the library's forward-rows
     switch) are read at every call and the kernels' ranges are asked of the library.  kr: the call
     carries key ranges, which the small kernels, the 64-row forward and the 64-row backward do
-    not take."""
+    not take.  drop: the call carries attention dropout: "small", "short" and "fused" have no
+    masked form and decline; the answer is "mh" where the multi-head kernels take the call and
+    the mask's counter covers it, else "gemm"."""
     dh = E // H
     half = cd != torch.float32
     if fwd is None:
@@ -1017,7 +1035,9 @@ def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=Non
         # the multi-head kernels: asked last, after "small", "short" and "fused" have declined
         mh = lambda: (half and aligned and
                       ops.attn_mh_ok(_dc(cd), dh, N, H, Lq, Lk, q.stride, k.stride, v.stride))
-        if kr:
+        if drop:
+            fwd = "mh" if mh() and _attn_drop_counter_ok(N, H, Lq) else "gemm"
+        elif kr:
             if half and aligned and ops.attn_short_ok(_dc(cd), dh, Lq, Lk):
                 fwd = "short"
             elif (half and ops.attn_supported(_dc(cd), dh) and
@@ -1056,14 +1076,21 @@ def attn_plan(cd, N, H, Lq, Lk, E, q, k, v, o, go=None, dq=None, dk=None, dv=Non
     return AttnPlan(fwd, rows, bwd, rows and bwd == "pds_dkdv")
 
 
-def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None, kr=None):
+def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None, kr=None, drop_p=0.0):
     """softmax(Q K^T / sqrt(dh)) V on seq-first strided views (see AttnCoreFn).  Returns the
     output (Lq, N, E) (memory order of q_src's rows) and the state attn_backward needs.
     qshare = (spp, qtab): sequence p spp + b reads the Q rows of sequence qtab[p] spp + b
     (ops.attn_fwd_sq; the caller has asked attn_plan with its gradient layouts).
     kr: a KeyRanges; sequence n attends to the keys of its entry n % kr.B only.  A call with
-    ranges never runs unmasked: attn_plan sends it to a kernel that takes the table."""
+    ranges never runs unmasked: attn_plan sends it to a kernel that takes the table.
+    drop_p: dropout on the probabilities, O = dropout(softmax(S)) V, at the rate
+    attn_dropout_rate(drop_p).  The call takes one state copy (ops.dropout_next: one `call` for
+    the whole launch) and keeps (p, copy) for its backward.  A rate that rounds to 0 (and 0 itself)
+    takes no copy and launches exactly the kernels of a call without dropout."""
     cd = compute_dtype()
+    drop_p = _check_rate(drop_p)
+    if drop_p > 0.0 and attn_dropout_rate(drop_p) == 0.0:
+        drop_p = 0.0
     for t in (q_src, k_src, v_src):
         assert t.dtype == cd and t.stride(-1) == 1
     Lq, N = q_src.shape[0], q_src.shape[1]
@@ -1080,12 +1107,18 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None, kr=No
                              "keys")
         kr = kr.op
     plan = attn_plan(cd, N, H, Lq, Lk, E, _operand(q_src, qcol, cd), _operand(k_src, kcol, cd),
-                     _operand(v_src, vcol, cd), _operand(o, 0, cd), kr=kr is not None)
+                     _operand(v_src, vcol, cd), _operand(o, 0, cd), kr=kr is not None,
+                     drop=drop_p > 0.0)
+    drop = (drop_p, ops.dropout_next(_drop_block(dev))) if drop_p > 0.0 else None
     if qshare is not None and not (plan.fwd == "fused" and plan.rows):
         raise JMTError("attn_forward: qshare on an unsupported shape")
     if kr is not None and (plan.fwd == "small" or (plan.fwd == "fused" and not plan.rows)):
         raise JMTError(f"attn_forward: key ranges on a path that takes none ({plan.fwd})")
     krk = {} if kr is None else {"kr": kr}
+    if drop is not None:
+        assert plan.fwd in ("mh", "gemm")
+        if plan.fwd == "mh":
+            krk["drop"] = drop
     if plan.fwd == "small":
         # short sequences (SELF_ATTEN head, intra-modal fusion): one wave per sequence, the
         # fp32 probabilities (N*H*Lq*Lk floats) kept for the backward (small_attn.hip)
@@ -1114,14 +1147,19 @@ def attn_forward(q_src, k_src, v_src, E, H, qcol, kcol, vcol, qshare=None, kr=No
         tensors = (q_src, k_src, v_src, None, o, lse)
     else:
         P = AttnCoreFn._probs(q_src, k_src, E, H, qcol, kcol, ldS, scale, cd, kr)
+        Pv = P
+        if drop is not None:
+            # the unmasked P stays for the backward; P~ = M o P feeds the P V GEMM only
+            Pv = torch.empty_like(P)
+            ops.attn_dropout(P, ldS, Pv, ldS, N * H, Lq, Lk, drop[0], drop[1])
         ops.gemm(M=Lq, N=dh, K=Lk, ab_dtype=_dc(cd), c_dtype=_dc(cd),
-                 a=[P.data_ptr()], lda=ldS, a_kmajor=True, sA=bS,
+                 a=[Pv.data_ptr()], lda=ldS, a_kmajor=True, sA=bS,
                  b=[_ptr(v_src, vcol)], ldb=v_src.stride(0), b_kmajor=False,
                  sB=(v_src.stride(1), dh),
                  c=[o.data_ptr()], ldc=o.stride(0), sC=(o.stride(1), dh),
                  batch0=N, batch1=H, device=dev)
         tensors = (q_src, k_src, v_src, P, None, None)
-    return o, (tensors, AttnMeta(E, H, qcol, kcol, vcol, ldS, scale, cd, plan.fwd, kr))
+    return o, (tensors, AttnMeta(E, H, qcol, kcol, vcol, ldS, scale, cd, plan.fwd, kr, drop))
 
 
 def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
@@ -1131,7 +1169,7 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
     dQ = dS_i K_i + dS_j K_j per shared query in its first use's rows of dq, the second use's
     rows left unwritten.  The path is attn_plan's answer for the buffers as they are handed in."""
     (q_src, k_src, v_src, *_), meta = saved
-    E, H, qcol, kcol, vcol, _, _, cd, fwd, kr = meta
+    E, H, qcol, kcol, vcol, _, _, cd, fwd, kr, drop = meta
     Lq, N = q_src.shape[0], q_src.shape[1]
     Lk = k_src.shape[0]
     v8 = _vec(cd)
@@ -1171,8 +1209,13 @@ def attn_backward(saved, go, dq, dk, dv, qshare=None, merge_dq=False):
 def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
     """The launches of attn_backward's path `bwd` (attn_plan) on normalised buffers."""
     (q_src, k_src, v_src, P, o, lse), meta = saved
-    E, H, qcol, kcol, vcol, ldS, scale, cd, _, kr = meta
+    E, H, qcol, kcol, vcol, ldS, scale, cd, _, kr, drop = meta
     krk = {} if kr is None else {"kr": kr}
+    if drop is not None:
+        if bwd not in ("mh", "gemm"):
+            raise JMTError(f"attn_backward: attention dropout on a path without a mask ({bwd})")
+        if bwd == "mh":
+            krk["drop"] = drop
     Lq, N = q_src.shape[0], q_src.shape[1]
     Lk = k_src.shape[0]
     dh = E // H
@@ -1251,6 +1294,9 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
                  a=[go.data_ptr()], lda=so_l, a_kmajor=True, sA=(so_n, dh),
                  b=[_ptr(v_src, vcol)], ldb=sv_l, b_kmajor=True, sB=(sv_n, dh),
                  c=[dP.data_ptr()], ldc=ldS, sC=bS, batch0=N, batch1=H, device=dev)
+        if drop is not None:
+            # dP = M o (dO V^T) in place; the softmax backward takes the unmasked P
+            ops.attn_dropout(dP, ldS, dP, ldS, N * H, Lq, Lk, drop[0], drop[1])
         ops.softmax_bwd(P, ldS, dP, ldS, N * H * Lq, Lk, scale, dS, ldS)
         del dP
         # dQ = dS K
@@ -1265,6 +1311,12 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
              b=[_ptr(q_src, qcol)], ldb=sq_l, b_kmajor=False, sB=(sq_n, dh),
              c=[_ptr(dk, kcol)], ldc=dk.stride(0), sC=(dk.stride(1), dh), batch0=N,
              batch1=H, device=dev)
+    if drop is not None:
+        # dV = P~^T dO with the forward's P~ regenerated (out of place: P is a saved tensor, a
+        # retained graph reads it again)
+        Pm = torch.empty_like(P)
+        ops.attn_dropout(P, ldS, Pm, ldS, N * H, Lq, Lk, drop[0], drop[1])
+        P = Pm
     # dV = P^T dO  (on the side stream, concurrent with dK, measured slower: the join waits
     # for the weight gradients queued there before it; profiles/r02_side_stream.txt)
     ops.gemm(M=Lk, N=dh, K=Lq, ab_dtype=_dc(cd), c_dtype=_dc(cd),
@@ -1274,29 +1326,31 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
              batch1=H, device=dev)
 
 
-def multihead_attention(query, key, value, in_w, in_b, out_w, out_b, num_heads, kr=None):
-    """nn.MultiheadAttention(E, H)(query, key, value) with dropout 0, seq-first (L, N, E).
+def multihead_attention(query, key, value, in_w, in_b, out_w, out_b, num_heads, kr=None,
+                        dropout_p=0.0):
+    """nn.MultiheadAttention(E, H, dropout=dropout_p)(query, key, value) in training mode (pass
+    0 in eval), seq-first (L, N, E).
     Every reference call site passes key is value: then K and V come from
     one packed in_proj GEMM (and Q too for self-attention).  kr: the KeyRanges of a
-    key_padding_mask."""
+    key_padding_mask.  dropout_p: on the attention probabilities (attn_forward's drop_p)."""
     E = in_w.shape[1]
     if query is key and key is value:
         qkv = linear(query, in_w, in_b, 0, 3 * E)
-        o = AttnCoreFn.apply(qkv, qkv, qkv, E, num_heads, 0, E, 2 * E, kr)
+        o = AttnCoreFn.apply(qkv, qkv, qkv, E, num_heads, 0, E, 2 * E, kr, dropout_p)
     elif key is value:
         q = linear(query, in_w, in_b, 0, E)
         kv = linear(key, in_w, in_b, E, 2 * E)
-        o = AttnCoreFn.apply(q, kv, kv, E, num_heads, 0, 0, E, kr)
+        o = AttnCoreFn.apply(q, kv, kv, E, num_heads, 0, 0, E, kr, dropout_p)
     else:
         q = linear(query, in_w, in_b, 0, E)
         k = linear(key, in_w, in_b, E, E)
         v = linear(value, in_w, in_b, 2 * E, E)
-        o = AttnCoreFn.apply(q, k, v, E, num_heads, 0, 0, 0, kr)
+        o = AttnCoreFn.apply(q, k, v, E, num_heads, 0, 0, 0, kr, dropout_p)
     return linear(o, out_w, out_b)
 
 
 def multihead_attention_shared_query(query, keys, in_w, in_b, out_w, out_b, num_heads,
-                                     kr=None):
+                                     kr=None, dropout_p=0.0):
     """[nn.MultiheadAttention(query, k, k) for k in keys] with ONE query projection: the
     reference applies each cross_attention_* module twice to the same query
     (mm_multi_transformers.py:142-167), so the q = query W_q^T + b_q GEMM is computed once."""
@@ -1305,7 +1359,7 @@ def multihead_attention_shared_query(query, keys, in_w, in_b, out_w, out_b, num_
     outs = []
     for key in keys:
         kv = linear(key, in_w, in_b, E, 2 * E)
-        o = AttnCoreFn.apply(q, kv, kv, E, num_heads, 0, 0, E, kr)
+        o = AttnCoreFn.apply(q, kv, kv, E, num_heads, 0, 0, E, kr, dropout_p)
         outs.append(linear(o, out_w, out_b))
     return outs
 

@@ -39,8 +39,8 @@ from torch.autograd import Function
 from . import linear_gemm as lg
 from . import ops, streams
 from .functional import (AttnOperand, Rows, _cast_keep_layout, _grad_buffer, _grad_done, _match,
-                         _operand, _out, _ptr, attn_backward, attn_forward, attn_plan,
-                         compute_dtype, weight_as, wgrad_defer_ok, wgrad_scope)
+                         _operand, _out, _ptr, attn_backward, attn_dropout_rate, attn_forward,
+                         attn_plan, compute_dtype, weight_as, wgrad_defer_ok, wgrad_scope)
 
 _enabled = {"on": os.environ.get("JMT_GROUPED", "1") != "0"}
 # the cross-attention backward's three stream-gradient GEMMs on branch streams: measured
@@ -227,7 +227,7 @@ class LastQueryMHAFn(Function):
     and no gradient sum."""
 
     @staticmethod
-    def forward(ctx, enc, Win, bin_, Wout, bout, H):
+    def forward(ctx, enc, Win, bin_, Wout, bout, H, drop_p=0.0):
         cd = compute_dtype()
         L, N, E = enc.shape
         X = Rows(enc, cd)                              # rows in enc's memory order
@@ -237,7 +237,7 @@ class LastQueryMHAFn(Function):
         XL = Rows(xl)
         q = XL.like(E, cd)
         lg.fwd(XL.op(), XL.rows, Win, bin_, _out(q, XL.perm), cd, 0, E)
-        o, asaved = attn_forward(q, kv, kv, E, H, 0, 0, E)
+        o, asaved = attn_forward(q, kv, kv, E, H, 0, 0, E, drop_p=drop_p)
         O = Rows(o)
         y = O.like(E, cd)
         lg.fwd(O.op(), O.rows, Wout, bout, _out(y, O.perm), cd)
@@ -272,12 +272,24 @@ class LastQueryMHAFn(Function):
         if xdt != cd:
             dx = _cast_keep_layout(dx, xdt)
         ctx.asaved = None
-        return dx, None, None, None, None, None
+        return dx, None, None, None, None, None, None
+
+
+def attn_drop_rate(modules) -> float:
+    """The attention dropout rate of the MultiheadAttention modules one launch serves (their
+    `dropout` while training, 0 in eval; modules without the attribute count as 0).  One launch
+    takes one mask call and one rate: modules that disagree raise ValueError."""
+    rates = {float(m.drop_rate()) if hasattr(m, "drop_rate") else 0.0 for m in modules}
+    if len(rates) > 1:
+        raise ValueError(f"attention modules of one grouped launch disagree on dropout: "
+                         f"{sorted(rates)}")
+    p = rates.pop() if rates else 0.0
+    return p if p > 0.0 and attn_dropout_rate(p) > 0.0 else 0.0     # below 1 / 512: none
 
 
 def last_query_mha(enc, mha) -> torch.Tensor:
     return LastQueryMHAFn.apply(enc, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                                mha.out_proj.bias, mha.num_heads)
+                                mha.out_proj.bias, mha.num_heads, attn_drop_rate([mha]))
 
 
 # ------------------------------------------------------------------------- encoder group
@@ -305,7 +317,7 @@ class EncoderGroupFn(Function):
 
     @staticmethod
     def forward(ctx, X, meta, *params):
-        H, eps1, eps2, batch_axis, kr = meta
+        H, eps1, eps2, batch_axis, kr, drop_p = meta
         if kr is not None and batch_axis:
             raise NotImplementedError("a key padding mask over time with attention over the "
                                       "batch axis")
@@ -323,12 +335,14 @@ class EncoderGroupFn(Function):
         lg.fwd(sd(X), R, col(0), col(1), sd(QKV), cd)
         if batch_axis:
             # QKV[g] (B, T, 3E) read as seq-first (L = B, N = T): attention over the batch axis
-            outs = [attn_forward(QKV[g], QKV[g], QKV[g], E, H, 0, E, 2 * E) for g in range(G)]
+            outs = [attn_forward(QKV[g], QKV[g], QKV[g], E, H, 0, E, 2 * E, drop_p=drop_p)
+                    for g in range(G)]
             O = [o for o, _ in outs]                           # G x (B, T, E)
             asaved = [sv for _, sv in outs]
         else:
             sf = QKV.view(G * B, T, 3 * E).permute(1, 0, 2)      # (T, G*B, 3E) seq-first
-            o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, kr=kr)  # memory (G*B, T, E)
+            # memory (G*B, T, E); with dropout one mask call for the whole launch
+            o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, kr=kr, drop_p=drop_p)
             O = o.permute(1, 0, 2)
         A1 = torch.empty(G, B, T, E, dtype=cd, device=dev)
         lg.fwd(lg.table(O, E) if batch_axis else lg.strided(O, E, R * E), R, col(2), col(3),
@@ -497,10 +511,11 @@ class EncoderGroupFn(Function):
 
 def encoder_group(X, layers, num_heads: int, batch_axis: bool = False, kr=None):
     """Apply `layers` (one TransformerEncoderLayer per stream) to the stacked X (attention over
-    T, or over B with batch_axis).  kr: the KeyRanges of a (B, T) key padding mask."""
+    T, or over B with batch_axis).  kr: the KeyRanges of a (B, T) key padding mask.  Attention
+    dropout: the layers' attention modules' rate (attn_drop_rate)."""
     params = [p for layer in layers for p in encoder_layer_params(layer)]
     meta = (num_heads, layers[0].layer_norm1.eps, layers[0].layer_norm2.eps, bool(batch_axis),
-            kr)
+            kr, attn_drop_rate([layer.attention for layer in layers]))
     return EncoderGroupFn.apply(X, meta, *params)
 
 
@@ -540,7 +555,7 @@ class CrossAttention6Fn(Function):
 
     @staticmethod
     def forward(ctx, Y, meta, *params):
-        H, pairs, kr = meta
+        H, pairs, kr, drop_p = meta
         cd = compute_dtype()
         Y = _contig(Y, cd)
         S, B, T, E = Y.shape
@@ -558,8 +573,9 @@ class CrossAttention6Fn(Function):
             # batch-major (NP * B, T, E) with row stride E
             oq, ok, ov = (_operand(sf, c, cd) for c in (0, E, 2 * E))
             od = AttnOperand(True, E)
+            # (with dropout the plan is "mh" or "gemm", never shared: every pair projects its own)
             if not attn_plan(cd, NP * B, H, T, T, E, oq, ok, ov, od, od, oq, ok, ov,
-                             kr=kr is not None).shared_q:
+                             kr=kr is not None, drop=drop_p > 0.0).shared_q:
                 qtab = None
         # queries and packed key/values, one launch each.  Shared queries: the projection of the
         # first use only (the q columns of the other uses' rows of QKV stay unused); otherwise
@@ -577,7 +593,8 @@ class CrossAttention6Fn(Function):
             lg.fwd(lg.table([Y[k] for _, _, k in pairs], E), R, in_w, in_b,
                    lg.strided((QKV, E), 3 * E, R * 3 * E), cd, E, 2 * E)
         qshare = (B, qtab) if qtab is not None else None
-        o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, qshare=qshare, kr=kr)
+        o, asaved = attn_forward(sf, sf, sf, E, H, 0, E, 2 * E, qshare=qshare, kr=kr,
+                                 drop_p=drop_p)
         O = o.permute(1, 0, 2)                                   # (NP*B, T, E) memory
         O6 = torch.empty(NP, B, T, E, dtype=cd, device=dev)
         lg.fwd(lg.strided(O, E, R * E), R, [M[m][2] for m, _, _ in pairs],
@@ -757,7 +774,7 @@ class CrossAttention6Fn(Function):
 
 def cross_attention6(Y, modules, num_heads: int, pairs=CROSS_PAIRS, kr=None):
     params = [p for mod in modules for p in mha_params(mod)]
-    return CrossAttention6Fn.apply(Y, (num_heads, pairs, kr), *params)
+    return CrossAttention6Fn.apply(Y, (num_heads, pairs, kr, attn_drop_rate(modules)), *params)
 
 
 # ------------------------------------------------------------------------- concat head

@@ -55,8 +55,11 @@ class _OutProj(Linear):
 
 
 class MultiheadAttention(nn.Module):
-    """Drop-in for nn.MultiheadAttention(embed_dim, num_heads) with dropout 0, seq-first inputs
-    and the packed `in_proj_weight` / `in_proj_bias` + `out_proj` parameters.  forward returns
+    """Drop-in for nn.MultiheadAttention(embed_dim, num_heads, dropout=p), seq-first inputs
+    and the packed `in_proj_weight` / `in_proj_bias` + `out_proj` parameters.  dropout acts on
+    the attention probabilities while the module trains (torch's semantics), with a counter-based
+    mask of 8 bits per element: the rate in effect is quantised to 1 / 256
+    (jmt.functional.attn_dropout_rate).  forward returns
     (attn_output, None): the head-averaged weights torch also returns are discarded by every
     reference call site and are not materialised.  key_padding_mask: contiguous
     padding only (key ranges); attn_mask, is_causal and float masks raise."""
@@ -64,8 +67,8 @@ class MultiheadAttention(nn.Module):
     def __init__(self, embed_dim: int, num_heads: int, dropout: float = 0.0, bias: bool = True):
         super().__init__()
         assert embed_dim % num_heads == 0, "embed_dim must be divisible by num_heads"
-        if dropout != 0.0:
-            raise NotImplementedError("attention dropout is not on the JMT path (p=0)")
+        F.attn_dropout_rate(dropout)            # raises for a rate the mask cannot express
+        self.dropout = float(dropout)
         self.embed_dim = embed_dim
         self.num_heads = num_heads
         self.head_dim = embed_dim // num_heads
@@ -89,8 +92,22 @@ class MultiheadAttention(nn.Module):
         kr = F.key_ranges(key_padding_mask) if key_padding_mask is not None else None
         out = F.multihead_attention(query, key, value, self.in_proj_weight, self.in_proj_bias,
                                     self.out_proj.weight, self.out_proj.bias, self.num_heads,
-                                    kr=kr)
+                                    kr=kr, dropout_p=self.drop_rate())
         return out, None
+
+    def drop_rate(self) -> float:
+        """The attention dropout rate in effect: `dropout` while training, 0 in eval."""
+        return float(self.dropout or 0.0) if self.training else 0.0
+
+
+def set_attention_dropout(module: nn.Module, p: float) -> nn.Module:
+    """Set attention dropout `p` on every jmt.nn.MultiheadAttention below `module` (the models'
+    constructors take no such argument: the reference never sets it)."""
+    F.attn_dropout_rate(p)
+    for m in module.modules():
+        if isinstance(m, MultiheadAttention):
+            m.dropout = float(p)
+    return module
 
 
 class MLP(nn.Sequential):

@@ -795,31 +795,44 @@ def attn_mh_ok(dtype: int, dh: int, N: int, H: int, Lq: int, Lk: int, sq_l: int,
             bool(_lib.load().jmt_attn_mh_ok(dtype, dh, N, H, Lq, Lk, sq_l, sk_l, sv_l)))
 
 
+def _mh_tail(base, kr, drop):
+    """Entry point and trailing arguments of a multi-head attention call: `base`, `base`_kr or,
+    with drop = (p, counter block), `base`_drop (range table or NULL, kr_mod, p, ctr)."""
+    if drop is None:
+        return (base if kr is None else base + "_kr"), _kr_args(kr)
+    p, ctr = drop
+    _require_cuda(ctr)
+    return base + "_drop", ((_kr_args(kr) or (None, 1)) + (float(p), ctr.data_ptr()))
+
+
 def attn_mh_fwd(dtype, N, H, Lq, Lk, dh, q_ptr, sq, k_ptr, sk, v_ptr, sv, o_ptr, so, scale, lse,
-                kr=None):
+                kr=None, drop=None):
     """Flash-attention forward for dh 64 / 128 (o and lse; one block per 64 query rows of an
-    (n, h)); kr: key ranges as attn_fwd (jmt_attn_mh_fwd_kr)."""
-    name = "jmt_attn_mh_fwd" if kr is None else "jmt_attn_mh_fwd_kr"
+    (n, h)); kr: key ranges as attn_fwd (jmt_attn_mh_fwd_kr); drop = (p, ctr): dropout on the
+    probabilities with the mask of the state copy ctr (jmt_attn_mh_fwd_drop)."""
+    name, tail = _mh_tail("jmt_attn_mh_fwd", kr, drop)
     launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, q_ptr, sq[0], sq[1],
                                k_ptr, sk[0], sk[1], v_ptr, sv[0], sv[1], o_ptr, so[0], so[1],
                                scale, lse.data_ptr() if lse is not None else None,
-                               *_kr_args(kr), stream())
+                               *tail, stream())
     # bytes: q, k, v read, o and lse written
     _hooked({"family": "attn_mh_fwd", "flops": 4.0 * N * H * Lq * Lk * dh,
              "bytes": float(N * H) * ((2 * Lq + 2 * Lk) * dh * 2 + 4 * Lq)}, launch)
 
 
 def attn_mh_bwd(dtype, N, H, Lq, Lk, dh, go_ptr, sgo, o_ptr, so, q_ptr, sq, k_ptr, sk, v_ptr,
-                sv, lse, dq_ptr, sdq, dk_ptr, sdk, dv_ptr, sdv, scale, delta, kr=None):
+                sv, lse, dq_ptr, sdq, dk_ptr, sdk, dv_ptr, sdv, scale, delta, kr=None,
+                drop=None):
     """dQ, dK, dV of attn_mh_fwd: the dQ kernel (which also writes delta = rowsum(dO o O), N H Lq
     floats) and the dK / dV kernel behind one entry point, P recomputed from lse in both, no
-    atomics; kr: the forward's key ranges (jmt_attn_mh_bwd_kr)."""
-    name = "jmt_attn_mh_bwd" if kr is None else "jmt_attn_mh_bwd_kr"
+    atomics; kr: the forward's key ranges (jmt_attn_mh_bwd_kr); drop: the forward's (p, ctr),
+    from which both kernels regenerate its mask (jmt_attn_mh_bwd_drop)."""
+    name, tail = _mh_tail("jmt_attn_mh_bwd", kr, drop)
     launch = lambda: _lib.call(name, dtype, N, H, Lq, Lk, dh, go_ptr, sgo[0],
                                sgo[1], o_ptr, so[0], so[1], q_ptr, sq[0], sq[1], k_ptr, sk[0],
                                sk[1], v_ptr, sv[0], sv[1], lse.data_ptr(), dq_ptr, sdq[0], sdq[1],
                                dk_ptr, sdk[0], sdk[1], dv_ptr, sdv[0], sdv[1], scale,
-                               delta.data_ptr(), *_kr_args(kr), stream())
+                               delta.data_ptr(), *tail, stream())
     # algorithmic: the five products of a flash backward (S, dP, dV, dK, dQ); bytes: q, k, v, o,
     # dO read, dq, dk, dv written, lse read, delta written
     _hooked({"family": "attn_mh_bwd", "flops": 10.0 * N * H * Lq * Lk * dh,
@@ -983,6 +996,36 @@ def dropout_reference(ctr, rows, cols, split, p0, p1):
     words = (C.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in ctr])
     out = np.empty((rows, cols), dtype=np.float32)
     _lib.call("jmt_dropout_reference", words, rows, cols, split, float(p0), float(p1),
+              out.ctypes.data_as(_lib.c_fp))
+    return out
+
+
+def attn_dropout_rate(p) -> float:
+    """The rate in effect of attention dropout p: T8 / 256 with T8 = floor(256 p + 1/2)
+    (jmt_attn_dropout_rate; no GPU call).  Raises for p outside [0, 1) or with T8 > 255."""
+    r = float(_lib.load().jmt_attn_dropout_rate(float(p)))
+    if r < 0.0:
+        raise _lib.JMTError(f"attention dropout rate {p}: outside [0, 1) or above 255.5 / 256")
+    return r
+
+
+def attn_dropout(x, ldx, y, ldy, NH, Lq, Lk, p, ctr):
+    """y = M o x on an (NH Lq, ld) buffer of probabilities or of dP (jmt_attn_dropout: the
+    attention mask of state copy ctr; y may be x; out of place the columns [Lk, ldy) become 0)."""
+    _require_cuda(x, y, ctr)
+    launch = lambda: _lib.call("jmt_attn_dropout", dt(x), x.data_ptr(), ldx, y.data_ptr(), ldy,
+                               NH, Lq, Lk, float(p), ctr.data_ptr(), stream())
+    es = x.element_size()
+    _hooked({"family": "attn_dropout", "flops": 0.0, "bytes": 2.0 * NH * Lq * Lk * es}, launch)
+
+
+def attn_dropout_reference(ctr, NH, Lq, Lk, p):
+    """Host only: the (NH, Lq, Lk) fp32 multipliers of state block `ctr` (4 ints) as a numpy
+    array (jmt_attn_dropout_reference)."""
+    import numpy as np
+    words = (C.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in ctr])
+    out = np.empty((NH, Lq, Lk), dtype=np.float32)
+    _lib.call("jmt_attn_dropout_reference", words, NH, Lq, Lk, float(p),
               out.ctypes.data_as(_lib.c_fp))
     return out
 

@@ -160,7 +160,8 @@ class MultimodalTransformer_w_JR(nn.Module):
         def ca(mod, query, keys):
             return F.multihead_attention_shared_query(
                 query, keys, mod.in_proj_weight, mod.in_proj_bias, mod.out_proj.weight,
-                mod.out_proj.bias, mod.num_heads, **({} if kr is None else {"kr": kr}))
+                mod.out_proj.bias, mod.num_heads, dropout_p=mod.drop_rate(),
+                **({} if kr is None else {"kr": kr}))
 
         r_v, r_p, r_pv = streams.run_parallel(
             [lambda: ca(self.cross_attention_v, v, (p, j)),
