@@ -146,8 +146,8 @@ class GradBucketer:
         self.bucket_left = [b[2] for b in self.buckets]
         self.launched = [False] * len(self.buckets)
         # streams that enqueued a write of each bucket's parameters (the compute stream, the
-        # weight-gradient side stream, the run_parallel branch streams, ...): the bucket's
-        # all-reduce is ordered after ALL of them, not only after the stream of its last write
+        # run_parallel branch streams): the bucket's all-reduce is ordered after ALL of them,
+        # not only after the stream of its last write
         self.writers = [[] for _ in self.buckets]
         self.works = []
         self.launch_log = []
@@ -193,13 +193,11 @@ class GradBucketer:
                 collective(issue)
                 return
             # every stream that wrote one of the bucket's gradients (recorded by _done), the
-            # stream this last notification came from, the weight-gradient side stream
-            # (jmt.streams.run_side) and the step's compute stream precede the all-reduce; a
-            # wait is one event record + one stream wait, no host synchronisation
-            from . import streams
+            # stream this last notification came from and the step's compute stream precede the
+            # all-reduce; a wait is one event record + one stream wait, no host synchronisation
             cur = torch.cuda.current_stream()
             waits = list(self.writers[b])
-            for st in [cur] + streams.side_streams() + [self._main]:
+            for st in (cur, self._main):
                 if st is not None and st.device == cur.device and st not in waits:
                     waits.append(st)
             for st in waits:

@@ -250,10 +250,8 @@ def wgrad_group_ok() -> bool:
 def wgrad_defer_ok(cd) -> bool:
     """Whether a weight gradient of compute dtype `cd` whose operands stay intact may be held
     until the end of the backward pass (ops: stage B, defer="late"): where grouping is allowed
-    and the grouped launch takes the operands (16-bit), unless JMT_WGRAD_DEFER=0 or the side
-    stream is on (its launches overlap the dgrad chain where they are issued)."""
-    return (wgrad_group_ok() and cd != torch.float32 and ops.wgrad_defer_mode() != "off" and
-            not streams.side_enabled())
+    and the grouped launch takes the operands (16-bit), unless JMT_WGRAD_DEFER=0."""
+    return wgrad_group_ok() and cd != torch.float32 and ops.wgrad_defer_mode() != "off"
 
 
 def wgrad_scope(cd=torch.float32):
@@ -334,14 +332,10 @@ class LinearFn(Function):
                 if need[i]:
                     dxs[i] = outs[i] if in_dtypes[i] == cd else _cast_keep_layout(outs[i],
                                                                                   in_dtypes[i])
-
-        def param_grads():      # side stream (jmt.streams.run_side)
-            # no input gradient: nothing runs behind this node that could write gy or the
-            # saved inputs, so the launch may join the end-of-backward group
-            lg.wgrad(Gy.op(), lg.table(xin, L0.ld), Gy.rows, n, W, cd, b, r0, kseg,
-                     defer=not any(need))
-
-        streams.run_side(param_grads, reads=(Gy.t,) + tuple(xin))
+        # no input gradient: nothing runs behind this node that could write gy or the saved
+        # inputs, so the launch may join the end-of-backward group
+        lg.wgrad(Gy.op(), lg.table(xin, L0.ld), Gy.rows, n, W, cd, b, r0, kseg,
+                 defer=not any(need))
         return (None, None, None, None, None, None, *dxs)
 
 
@@ -454,23 +448,18 @@ class MLPFn(Function):
         lg.dgrad(Gy.op(), Gy.rows, nout, W2, lg.strided(dh, ldh), cd, aux=h, ldaux=H.ld)
         if ctr is not None:
             ops.dropout(dh, ldh, dh, ldh, L.rows, hid, hid, p, p, ctr)
-
-        def w2_grads():         # side stream (jmt.streams.run_side)
-            if odt == torch.float32 and cd != torch.float32 and nout <= 16:
-                # fp32 output (the V/A regressors' last layer, two_transformers.py:104-114): its
-                # weight / bias gradients are sums over all rows of the fp32 loss gradient,
-                # which nearly cancel (sum_i dL/dx_i = n c0 for the CCC): summing a 16-bit
-                # rounded copy would cost up to ~20 % relative error, so they are reduced from
-                # fp32 dY and an fp32 copy of the (small) hidden activations with the exact-f32
-                # MFMA GEMM.
-                G = _match(gy, Rows(L.like(nout, torch.float32)), torch.float32)
-                hx, dt = Rows(_cast_keep_layout(h, torch.float32)), torch.float32
-            else:
-                G, hx, dt = Gy, H, cd
-            lg.wgrad(G.op(), hx.op(), G.rows, nout, W2, dt)
-            lg.bias_grad(G.op(), G.rows, nout, [b2])
-
-        streams.run_side(w2_grads, reads=(gy, Gy.t, h))
+        if odt == torch.float32 and cd != torch.float32 and nout <= 16:
+            # fp32 output (the V/A regressors' last layer, two_transformers.py:104-114): its
+            # weight / bias gradients are sums over all rows of the fp32 loss gradient, which
+            # nearly cancel (sum_i dL/dx_i = n c0 for the CCC): summing a 16-bit rounded copy
+            # would cost up to ~20 % relative error, so they are reduced from fp32 dY and an
+            # fp32 copy of the (small) hidden activations with the exact-f32 MFMA GEMM.
+            G = _match(gy, Rows(L.like(nout, torch.float32)), torch.float32)
+            hx, dt = Rows(_cast_keep_layout(h, torch.float32)), torch.float32
+        else:
+            G, hx, dt = Gy, H, cd
+        lg.wgrad(G.op(), hx.op(), G.rows, nout, W2, dt)
+        lg.bias_grad(G.op(), G.rows, nout, [b2])
         Gh = Rows(dh)
         dx = None
         if ctx.needs_input_grad[5]:
@@ -478,11 +467,7 @@ class MLPFn(Function):
             lg.dgrad(Gh.op(), Gh.rows, hid, W1, _out(dx, L.perm), cd)
             if xdt != cd:
                 dx = _cast_keep_layout(dx, xdt)
-
-        def w1_grads():
-            lg.wgrad(Gh.op(), lg.strided(xin, L.ld), Gh.rows, hid, W1, cd, b1)
-
-        streams.run_side(w1_grads, reads=(dh, xin))
+        lg.wgrad(Gh.op(), lg.strided(xin, L.ld), Gh.rows, hid, W1, cd, b1)
         return None, None, None, None, None, dx, None
 
 
@@ -637,10 +622,6 @@ class MLPPairFn(Function):
         dh = L.like(2 * hid, cd)
         dhs = (dh[..., :hid], dh[..., hid:])
 
-        def w1_grads():         # one batched launch (+ one grouped column-sum launch pair)
-            lg.wgrad(lg.strided(dh, ldh, hid), lg.strided(xin, L.ld), L.rows, hid, (W1a, W1b),
-                     cd, (b1a, b1b), queue=False)
-
         gys = []
         for gy in (gya, gyb):
             if gy is None:
@@ -680,7 +661,9 @@ class MLPPairFn(Function):
                          _out(dx, L.perm), cd)
                 if xdt != cd:
                     dx = _cast_keep_layout(dx, xdt)
-            streams.run_side(w1_grads, reads=(dh, xin))
+            # one batched launch (+ one grouped column-sum launch pair)
+            lg.wgrad(lg.strided(dh, ldh, hid), lg.strided(xin, L.ld), L.rows, hid, (W1a, W1b),
+                     cd, (b1a, b1b), queue=False)
             return (None,) * 9 + (dx, None, None)
         Gys = [_match(gy, Rows(L.like(nout, cd)), cd) for gy in gys]
         if nout == 1 or Gys[0].ld == Gys[1].ld:
@@ -692,18 +675,13 @@ class MLPPairFn(Function):
                 lg.dgrad(Gy.op(), Gy.rows, nout, W2, lg.strided(dhp, ldh), cd, aux=hp, ldaux=ldh)
         if ctr is not None:
             ops.dropout(dh, ldh, dh, ldh, L.rows, 2 * hid, hid, p_a, p_b, ctr)
-
-        def w2_grads():         # side stream (jmt.streams.run_side), as in MLPFn
-            if odt == torch.float32 and cd != torch.float32 and nout <= 16:
-                h32 = _cast_keep_layout(h, torch.float32)
-                G32 = [_match(gy, Rows(L.like(nout, torch.float32)), torch.float32)
-                       for gy in gys]
-                MLPPairFn._w2_grads(G32, h32, _ld(h32, L.perm), hid, nout, (W2a, W2b),
-                                    (b2a, b2b), torch.float32)
-            else:
-                MLPPairFn._w2_grads(Gys, h, ldh, hid, nout, (W2a, W2b), (b2a, b2b), cd)
-
-        streams.run_side(w2_grads, reads=tuple(gys) + (h,) + tuple(G.t for G in Gys))
+        if odt == torch.float32 and cd != torch.float32 and nout <= 16:     # as in MLPFn
+            h32 = _cast_keep_layout(h, torch.float32)
+            G32 = [_match(gy, Rows(L.like(nout, torch.float32)), torch.float32) for gy in gys]
+            MLPPairFn._w2_grads(G32, h32, _ld(h32, L.perm), hid, nout, (W2a, W2b),
+                                (b2a, b2b), torch.float32)
+        else:
+            MLPPairFn._w2_grads(Gys, h, ldh, hid, nout, (W2a, W2b), (b2a, b2b), cd)
         dx = None
         if ctx.needs_input_grad[9]:
             dx = L.like(L.F, cd)
@@ -717,8 +695,9 @@ class MLPPairFn(Function):
             dx.add_(dxb)
             if xdt != cd:
                 dx = _cast_keep_layout(dx, xdt)
-
-        streams.run_side(w1_grads, reads=(dh, xin))
+        # one batched launch (+ one grouped column-sum launch pair)
+        lg.wgrad(lg.strided(dh, ldh, hid), lg.strided(xin, L.ld), L.rows, hid, (W1a, W1b),
+                 cd, (b1a, b1b), queue=False)
         return (None,) * 9 + (dx, None, None)
 
 
@@ -1317,8 +1296,7 @@ def _attn_backward_launch(bwd, saved, go, dq, dk, dv, qshare, merge_dq):
         Pm = torch.empty_like(P)
         ops.attn_dropout(P, ldS, Pm, ldS, N * H, Lq, Lk, drop[0], drop[1])
         P = Pm
-    # dV = P^T dO  (on the side stream, concurrent with dK, measured slower: the join waits
-    # for the weight gradients queued there before it; profiles/r02_side_stream.txt)
+    # dV = P^T dO
     ops.gemm(M=Lk, N=dh, K=Lq, ab_dtype=_dc(cd), c_dtype=_dc(cd),
              a=[P.data_ptr()], lda=ldS, a_kmajor=False, sA=bS,
              b=[go.data_ptr()], ldb=so_l, b_kmajor=False, sB=(so_n, dh),

@@ -16,7 +16,6 @@ Requirements the JMT path meets by construction:
 """
 from __future__ import annotations
 
-import os
 from typing import Callable, List, Optional, Tuple
 
 import torch
@@ -42,11 +41,7 @@ class GraphedStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        # JMT_COMPUTE_PRIO=1: capture on a high-priority stream, so the step's critical chain
-        # outranks the weight-gradient side stream (jmt.streams, default priority) when both
-        # have blocks waiting for CUs
-        cap = torch.cuda.Stream(priority=-1) if os.environ.get("JMT_COMPUTE_PRIO") == "1" else None
-        with torch.cuda.graph(self.graph, stream=cap):
+        with torch.cuda.graph(self.graph):
             self.out = self.step_fn()
         torch.cuda.synchronize()
         return self
@@ -88,10 +83,10 @@ class SegmentedStep:
     after an empty marker kernel (no segment is empty), queues the collective, and starts the
     next segment; replay() runs segment, collective, segment, ... in capture order on the
     current stream, so each bucket's all-reduce still overlaps the rest of the backward.
-    Requirements as GraphedStep, plus: no forked stream may be open across a collective (the
-    weight-gradient side stream is turned off while capturing), and the caller holds no output
-    of an earlier eager step (its autograd graph would keep the parameters' AccumulateGrad nodes,
-    created on another stream, so their hooks — the bucket notifications — run on that stream)."""
+    Requirements as GraphedStep, plus: no forked stream may be open across a collective, and
+    the caller holds no output of an earlier eager step (its autograd graph would keep the
+    parameters' AccumulateGrad nodes, created on another stream, so their hooks — the bucket
+    notifications — run on that stream)."""
 
     def __init__(self, step_fn: Callable[[], object]):
         self.step_fn = step_fn
@@ -101,7 +96,6 @@ class SegmentedStep:
         self._stream: Optional[torch.cuda.Stream] = None
 
     def capture(self, warmup: int = 3):
-        from . import streams
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -112,19 +106,14 @@ class SegmentedStep:
         self.pool = torch.cuda.graph_pool_handle()
         self._stream = torch.cuda.Stream()
         self._stream.wait_stream(torch.cuda.current_stream())
-        side_on = streams._enabled.get("side", True)
-        streams.set_side_enabled(False)
-        try:
-            with torch.cuda.stream(self._stream):
-                self._begin()
-                _capturing.append(self)
-                try:
-                    self.out = self.step_fn()
-                finally:
-                    _capturing.pop()
-                self._end(None)
-        finally:
-            streams.set_side_enabled(side_on)
+        with torch.cuda.stream(self._stream):
+            self._begin()
+            _capturing.append(self)
+            try:
+                self.out = self.step_fn()
+            finally:
+                _capturing.pop()
+            self._end(None)
         torch.cuda.current_stream().wait_stream(self._stream)
         torch.cuda.synchronize()
         return self

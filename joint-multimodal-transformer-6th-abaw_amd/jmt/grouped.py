@@ -29,7 +29,6 @@ Stacked layouts (compute dtype, row-major, rows in (b, t) order per group):
 """
 from __future__ import annotations
 
-import functools
 import os
 from typing import List
 
@@ -37,15 +36,12 @@ import torch
 from torch.autograd import Function
 
 from . import linear_gemm as lg
-from . import ops, streams
+from . import ops
 from .functional import (AttnOperand, Rows, _cast_keep_layout, _grad_buffer, _grad_done, _match,
                          _operand, _out, _ptr, attn_backward, attn_dropout_rate, attn_forward,
                          attn_plan, compute_dtype, weight_as, wgrad_defer_ok, wgrad_scope)
 
 _enabled = {"on": os.environ.get("JMT_GROUPED", "1") != "0"}
-# the cross-attention backward's three stream-gradient GEMMs on branch streams: measured
-# 1.6 % slower per step (profiles/r02_par_stream_dgrad.txt), off unless JMT_PAR_STREAM_DGRAD=1
-_PAR_STREAM_DGRAD = os.environ.get("JMT_PAR_STREAM_DGRAD", "0") == "1"
 
 # the six cross-attentions in the reference's order (mm_multi_transformers.py:142-167), which is
 # also the order of torch.cat in the FC head (:201-211): (module, query stream, key/value stream)
@@ -374,7 +370,6 @@ class EncoderGroupFn(Function):
     def backward(ctx, dY):
         G, B, T, E, hid, cd, batch_axis = ctx.meta
         X, QKV, asaved, O, A1, H1, st1, F1, F2, st2 = ctx.state
-        o_reads = tuple(O) if batch_axis else (O,)
         params = ctx.params
         P = [params[12 * g:12 * g + 12] for g in range(G)]
         R = B * T
@@ -436,8 +431,6 @@ class EncoderGroupFn(Function):
         # FFN (the ReLU mask is fused into the W2 dgrad epilogue)
         dF1 = torch.empty(G, B, T, hid, dtype=cd, device=dev)
         lg.dgrad(sd(dS), R, E, col(6), sd(dF1), cd, aux=F1, ldaux=hid)
-        # (W2's weight gradient stays on the compute stream: on the side stream the in-place
-        # dH1 below would have to wait for it, which measured slower, profiles/r02_side_stream.txt)
         # With hid == E, W1's weight gradient (dF1 and H1 are ready here) goes in the same launch:
         # 2 G entries of 512 x 512 over the B T rows (24 tiles at G = 3: the split-K ping-pong
         # kernel) instead of two 12-tile launches on the 128 x 128 split plan
@@ -467,12 +460,8 @@ class EncoderGroupFn(Function):
         # the queued W2 weight gradient's operand)
         dH1 = torch.empty_like(dS) if late else dS
         lg.dgrad(sd(dF1), R, hid, col(4), sd(dH1), cd, beta=1.0, c_in=dS if late else None)
-
-        def w1_grads():         # side stream: dF1 and H1 are not written again
-            lg.wgrad(sd(dF1), sd(H1), R, hid, col(4), cd, col(5), intact=late)
-
         if not merged:
-            streams.run_side(w1_grads, reads=(dF1, H1))
+            lg.wgrad(sd(dF1), sd(H1), R, hid, col(4), cd, col(5), intact=late)
         # LN1: dS1 = d(X + A1)
         dS1 = torch.empty_like(dS)
         bo_done = ln_bwd(X, A1, dH1, st1, [p[8] for p in P], [p[9] for p in P], dS1,
@@ -480,12 +469,8 @@ class EncoderGroupFn(Function):
         # out_proj
         dO = dH1    # reuse: dH1 is dead
         lg.dgrad(sd(dS1), R, E, col(2), sd(dO), cd)
-
-        def out_proj_grads():   # side stream, under the attention backward
-            lg.wgrad(sd(dS1), lg.table(O, E) if batch_axis else lg.strided(O, E, R * E), R, E,
-                     col(2), cd, None if bo_done else col(3), intact=late)
-
-        streams.run_side(out_proj_grads, reads=(dS1,) + o_reads)
+        lg.wgrad(sd(dS1), lg.table(O, E) if batch_axis else lg.strided(O, E, R * E), R, E,
+                 col(2), cd, None if bo_done else col(3), intact=late)
         # attention core -> packed dQKV
         dQKV = torch.empty(G, B, T, 3 * E, dtype=cd, device=dev)
         if batch_axis:
@@ -494,17 +479,12 @@ class EncoderGroupFn(Function):
         else:
             dsf = dQKV.view(G * B, T, 3 * E).permute(1, 0, 2)
             attn_backward(asaved, dO.view(G * B, T, E).permute(1, 0, 2), dsf, dsf, dsf)
-        # in_proj: dX = dS1 + dQKV . W_in  (in place on dS1, once the side stream has read it;
-        # stage B: into a fresh buffer, dS1 is the queued out_proj weight gradient's operand —
-        # the returned dX is accumulated into again downstream, StackJointFn)
-        streams.wait_side()
+        # in_proj: dX = dS1 + dQKV . W_in  (in place on dS1; stage B: into a fresh buffer, dS1 is
+        # the queued out_proj weight gradient's operand — the returned dX is accumulated into
+        # again downstream, StackJointFn)
         dX = torch.empty_like(dS1) if late else dS1
         lg.dgrad(sd(dQKV), R, 3 * E, col(0), sd(dX), cd, beta=1.0, c_in=dS1 if late else None)
-
-        def in_proj_grads():    # side stream: dQKV and X are not written again
-            lg.wgrad(sd(dQKV), sd(X), R, 3 * E, col(0), cd, col(1), intact=late)
-
-        streams.run_side(in_proj_grads, reads=(dQKV, X))
+        lg.wgrad(sd(dQKV), sd(X), R, 3 * E, col(0), cd, col(1), intact=late)
         ctx.state = None
         return (dX, None) + (None,) * len(params)
 
@@ -634,8 +614,7 @@ class CrossAttention6Fn(Function):
                 seen.append(set())
             halves[-1].append(i)
             seen[-1].add(m)
-        # out_proj: input gradient on the compute stream, weight / bias gradients on the side
-        # stream (jmt.streams.run_side) overlapping the attention backward
+        # out_proj: input gradient
         dO = torch.empty(NP, B, T, E, dtype=cd, device=dev)
         lg.dgrad(lg.strided(dO6, E, R * E), R, E, out_w, lg.strided(dO, E, R * E), cd)
 
@@ -655,62 +634,57 @@ class CrossAttention6Fn(Function):
         merge = (qtab is not None and _shared_q["merge"] and
                  all(qtab.count(i) == 2 for i in set(qtab)) and
                  (not kcat or all(qtab[i] == i and qtab[j] == i for i, j in zip(h0, h1))))
-
-        def out_proj_grads():
-            # (the launches take offsets into dO6 / O; only the column-sum fallback needs views)
-            kw = dict(intact=late, fallback=False)
-            if kcat:
-                if not lg.wgrad(lg.ksegs([[blk(dO6, i), blk(dO6, j)] for i, j in uses], E, R),
-                                lg.ksegs([[blk(O, i), blk(O, j)] for i, j in uses], E, R), R, E,
-                                sel(out_w, h0), cd, sel(out_b, h0), **kw):
-                    lg.bias_grad(lg.ksegs([[dO6[i], dO6[j]] for i, j in uses], E, R), R, E,
-                                 sel(out_b, h0))
-                return
+        # out_proj weight / bias gradients (the launches take offsets into dO6 / O; only the
+        # column-sum fallback needs views)
+        kw = dict(intact=late, fallback=False)
+        if kcat:
+            if not lg.wgrad(lg.ksegs([[blk(dO6, i), blk(dO6, j)] for i, j in uses], E, R),
+                            lg.ksegs([[blk(O, i), blk(O, j)] for i, j in uses], E, R), R, E,
+                            sel(out_w, h0), cd, sel(out_b, h0), **kw):
+                lg.bias_grad(lg.ksegs([[dO6[i], dO6[j]] for i, j in uses], E, R), R, E,
+                             sel(out_b, h0))
+        else:
             rest = [h for h in halves if not lg.wgrad(
                 lg.table([blk(dO6, i) for i in h], E), lg.table([blk(O, i) for i in h], E), R, E,
                 sel(out_w, h), cd, sel(out_b, h), **kw)]
             for h in rest:
                 lg.bias_grad(lg.table([dO6[i] for i in h], E), R, E, sel(out_b, h))
-
-        streams.run_side(out_proj_grads, reads=(dO6, O))
         # attention core -> packed dQKV (NP, B, T, 3E)
         dQKV = torch.empty(NP, B, T, 3 * E, dtype=cd, device=dev)
         dsf = dQKV.view(NP * B, T, 3 * E).permute(1, 0, 2)
         attn_backward(asaved, dO.view(NP * B, T, E).permute(1, 0, 2), dsf, dsf, dsf,
                       qshare=(B, qtab) if qtab is not None else None, merge_dq=merge)
 
-        # in_proj weight gradients (side stream, overlapping the stream dgrads): query rows
-        # [0, E) from the query stream, key/value rows [E, 3E) from the key stream
-        def in_proj_grads():
-            dq = lambda i, off=0: (dQKV, i * R * 3 * E + off)     # pair i's packed gradient rows
-            Yc = lambda i, c: blk(Y, pairs[i][c])                 # its query (1) / key (2) stream
-            kw = dict(intact=late, fallback=False)
-            # the query-row and key / value-row launches sit next to each other: one grouped
-            # launch (their rows of W.grad / b.grad are disjoint).  They share one bias: the key /
-            # value launch sums it only if the query launch did, else the whole rows go through
-            # the column sum afterwards
-            if kcat:
-                ws, bs = sel(in_w, h0), sel(in_b, h0)
-                seg = lambda off: lg.ksegs([[dq(i, off), dq(j, off)] for i, j in uses], 3 * E, R)
-                yseg = lambda c: lg.ksegs([[Yc(i, c), Yc(j, c)] for i, j in uses], E, R)
-                with wgrad_scope(cd):
-                    if merge:
-                        # the merged dQ against the query stream: a plain problem over K = B T
-                        fq = lg.wgrad(lg.table([dq(i) for i in h0], 3 * E),
-                                      lg.table([Yc(i, 1) for i in h0], E), R, E, ws, cd, bs, **kw)
+        # in_proj weight gradients: query rows [0, E) from the query stream, key/value rows
+        # [E, 3E) from the key stream
+        dq = lambda i, off=0: (dQKV, i * R * 3 * E + off)     # pair i's packed gradient rows
+        Yc = lambda i, c: blk(Y, pairs[i][c])                 # its query (1) / key (2) stream
+        # the query-row and key / value-row launches sit next to each other: one grouped launch
+        # (their rows of W.grad / b.grad are disjoint).  They share one bias: the key / value
+        # launch sums it only if the query launch did, else the whole rows go through the column
+        # sum afterwards
+        if kcat:
+            ws, bs = sel(in_w, h0), sel(in_b, h0)
+            seg = lambda off: lg.ksegs([[dq(i, off), dq(j, off)] for i, j in uses], 3 * E, R)
+            yseg = lambda c: lg.ksegs([[Yc(i, c), Yc(j, c)] for i, j in uses], E, R)
+            with wgrad_scope(cd):
+                if merge:
+                    # the merged dQ against the query stream: a plain problem over K = B T
+                    fq = lg.wgrad(lg.table([dq(i) for i in h0], 3 * E),
+                                  lg.table([Yc(i, 1) for i in h0], E), R, E, ws, cd, bs, **kw)
+                else:
+                    fq = lg.wgrad(seg(0), yseg(1), R, E, ws, cd, bs, **kw)
+                fkv = lg.wgrad(seg(E), yseg(2), R, 2 * E, ws, cd, bs if fq else None, E, **kw)
+            if not (fq and fkv):
+                assert not fq, "query-row bias sums fused without the key / value rows"
+                for b, (i, j) in zip(bs, uses):
+                    lg.bias_grad(lg.strided(dQKV[i], 3 * E), R, 3 * E, [b])
+                    if merge:       # the second use has key / value columns only
+                        lg.bias_grad(lg.strided(dQKV[j].view(R, 3 * E)[:, E:], 3 * E), R,
+                                     2 * E, [b], E)
                     else:
-                        fq = lg.wgrad(seg(0), yseg(1), R, E, ws, cd, bs, **kw)
-                    fkv = lg.wgrad(seg(E), yseg(2), R, 2 * E, ws, cd, bs if fq else None, E, **kw)
-                if not (fq and fkv):
-                    assert not fq, "query-row bias sums fused without the key / value rows"
-                    for b, (i, j) in zip(bs, uses):
-                        lg.bias_grad(lg.strided(dQKV[i], 3 * E), R, 3 * E, [b])
-                        if merge:       # the second use has key / value columns only
-                            lg.bias_grad(lg.strided(dQKV[j].view(R, 3 * E)[:, E:], 3 * E), R,
-                                         2 * E, [b], E)
-                        else:
-                            lg.bias_grad(lg.strided(dQKV[j], 3 * E), R, 3 * E, [b])
-                return
+                        lg.bias_grad(lg.strided(dQKV[j], 3 * E), R, 3 * E, [b])
+        else:
             rest = []
             for h in halves:
                 ws, bs = sel(in_w, h), sel(in_b, h)
@@ -735,15 +709,13 @@ class CrossAttention6Fn(Function):
                                  [b], c0)
             for h in rest:
                 lg.bias_grad(lg.table([dQKV[i] for i in h], 3 * E), R, 3 * E, sel(in_b, h))
-
-        streams.run_side(in_proj_grads, reads=(dQKV, Y))
         # stream gradients: every use of stream s (as a query: rows [0,E) of W_in; as a key /
         # value: rows [E,2E) and [2E,3E)) is one K-segment of ONE dgrad GEMM (K = nseg * E); a
         # merged dQ is one segment for both of its uses
         dY = torch.zeros(S, B, T, E, dtype=cd, device=dev) if any(
             not any(q == s or k == s for _, q, k in pairs) for s in range(S)) else \
             torch.empty(S, B, T, E, dtype=cd, device=dev)
-        launches = []
+        segs = []
         for s in range(S):
             dys, wts = [], []
             for i, (m, q, k) in enumerate(pairs):
@@ -754,20 +726,15 @@ class CrossAttention6Fn(Function):
                 if k == s:
                     dys += [(dQKV, i * R * 3 * E + E), (dQKV, i * R * 3 * E + 2 * E)]
                     wts += [(Wc, E * E), (Wc, 2 * E * E)]
-            if dys:     # (lg.dgrad: at most 8 K-segments per launch)
-                launches.append(functools.partial(
-                    lg.dgrad, lg.kcat(dys, 3 * E, E), R, E, lg.kcat(wts, E, E),
-                    lg.strided(dY[s], E), cd))
+            segs.append((dys, wts))
         # one launch per stream (600 128x128 tiles each, under one round of the chip's resident
-        # slots): on their own streams the three overlap each other's last-round tails
-        # (default: the three write different dY[s] — one grouped launch where
-        # lg.group16_scope takes them, two rounds of the persistent grid instead of three)
-        if _PAR_STREAM_DGRAD:
-            streams.run_parallel(launches, dev)
-        else:
-            with lg.group16_scope():
-                for f in launches:
-                    f()
+        # slots); the three write different dY[s] — one grouped launch where lg.group16_scope
+        # takes them, two rounds of the persistent grid instead of three
+        with lg.group16_scope():
+            for s, (dys, wts) in enumerate(segs):
+                if dys:     # (lg.dgrad: at most 8 K-segments per launch)
+                    lg.dgrad(lg.kcat(dys, 3 * E, E), R, E, lg.kcat(wts, E, E),
+                             lg.strided(dY[s], E), cd)
         ctx.state = None
         return (dY, None) + (None,) * len(params)
 
@@ -809,16 +776,12 @@ class ConcatLinearFn(Function):
         dy = _contig(dy, cd)
         dX = torch.empty_like(X)
         lg.dgrad(lg.strided(dy, N), R, N, W, lg.strided(dX, E, R * E), cd, kseg=E)
-
-        def param_grads():      # side stream: overlaps the dgrads of the cross-attentions
-            # the S K-segments share dY: segment 0 also takes its row sums (the bias grad).
-            # Stage B (ops: the end-of-backward group): dy is this node's incoming gradient
-            # (autograd has summed the regressors' into it before this node runs) and X its
-            # saved input; neither is written again
-            lg.wgrad(lg.strided(dy, N), lg.strided(X, E, R * E), R, N, W, cd, b, kseg=E,
-                     intact=True)
-
-        streams.run_side(param_grads, reads=(dy, X))
+        # the S K-segments share dY: segment 0 also takes its row sums (the bias grad).
+        # Stage B (ops: the end-of-backward group): dy is this node's incoming gradient
+        # (autograd has summed the regressors' into it before this node runs) and X its
+        # saved input; neither is written again
+        lg.wgrad(lg.strided(dy, N), lg.strided(X, E, R * E), R, N, W, cd, b, kseg=E,
+                 intact=True)
         return dX, None, None
 
 

@@ -9,13 +9,12 @@ forward node, so the backward overlaps the same way."""
 from __future__ import annotations
 
 import os
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, Sequence
 
 import torch
 
 _pool: dict = {}
-_enabled = {"on": True, "capture": os.environ.get("JMT_CAPTURE_STREAMS", "1") != "0",
-            "side": os.environ.get("JMT_SIDE_STREAM", "0") == "1"}
+_enabled = {"on": True, "capture": os.environ.get("JMT_CAPTURE_STREAMS", "1") != "0"}
 
 
 def set_enabled(on: bool) -> None:
@@ -93,96 +92,18 @@ def run_parallel(fns: Sequence[Callable[[], object]], device) -> list:
     return outs
 
 
-# ------------------------------------------------------------------ weight-gradient side stream
-# In a backward pass the input-gradient (dgrad) GEMMs form the critical chain; the weight- and
-# bias-gradient launches of a layer only read that layer's output gradient and saved input and
-# write parameter gradients.  They go to one side stream per device, forked from the compute
-# stream right after the output gradient is enqueued, so their blocks fill the CUs the chain's
-# launches leave idle (tile-quantised last rounds, epilogue bursts, latency-bound phases).
-_side: dict = {}
-_side_join = {"queued": None}    # graph task id whose end-of-backward join is queued
+_SIDE_REMOVED = ("the weight-gradient side stream (JMT_SIDE_STREAM=1) was removed: it measured "
+                 "slower than the single stream (DESIGN.md §4); unset JMT_SIDE_STREAM")
 
 
 def set_side_enabled(on: bool) -> None:
-    _enabled["side"] = bool(on)
+    """The switch of the removed weight-gradient side stream.  Still here because bench.py turns
+    it off around its probe steps and then restores what the environment asked for: off is the
+    only mode left, so False does nothing and True raises ValueError."""
+    if on:
+        raise ValueError(_SIDE_REMOVED)
 
 
-def side_enabled() -> bool:
-    """Whether run_side moves weight-gradient launches to the side stream."""
-    return _enabled["on"] and _enabled["side"]
-
-
-def side_streams() -> List[torch.cuda.Stream]:
-    """The side streams created so far (jmt.dist.GradBucketer gates its all-reduces on them)."""
-    return list(_side.values())
-
-
-def run_side(fn: Callable[[], object], reads: Sequence[Optional[torch.Tensor]] = ()):
-    """Enqueue fn() on the current device's side stream after everything already queued on the
-    current stream.  `reads`: tensors fn's kernels read that the caller may drop before they run
-    (marked used on the side stream for the caching allocator).  Parameter-gradient writes of
-    different streams must not target the same memory: callers move ALL writes of a gradient
-    buffer to the side stream.  The caller's stream joins the side stream at the end of the
-    backward pass (a queued autograd callback), before the optimizer reads the gradients."""
-    if not (_enabled["on"] and _enabled["side"]) or \
-            (torch.cuda.is_current_stream_capturing() and not _enabled["capture"]):
-        return fn()
-    main = torch.cuda.current_stream()
-    dev = main.device.index if main.device.index is not None else torch.cuda.current_device()
-    side = _side.get(dev)
-    if side is None:
-        side = _side[dev] = torch.cuda.Stream(device=main.device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        out = fn()
-    for t in reads:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            t.record_stream(side)
-    # one join per backward pass, keyed on autograd's graph task (a backward that raised
-    # before its final callbacks ran cannot leave a stale flag that skips later joins)
-    task = torch._C._current_graph_task_id()
-    if task < 0:                       # outside a backward: the caller joins (wait_side)
-        return out
-    if _side_join["queued"] != task:
-        _side_join["queued"] = task
-
-        def _cb():
-            _side_join["queued"] = None
-            cur = torch.cuda.current_stream()
-            for st in _side.values():
-                if st.device == cur.device:
-                    cur.wait_stream(st)
-
-        torch.autograd.Variable._execution_engine.queue_callback(_cb)
-    return out
-
-
-def wait_side() -> None:
-    """Make the current stream wait for the work queued so far on its device's side stream (a
-    kernel about to overwrite a buffer that side-stream work still reads)."""
-    cur = torch.cuda.current_stream()
-    for st in _side.values():
-        if st.device == cur.device:
-            cur.wait_stream(st)
-
-
-def fork_side(fn: Callable[[], object], reads: Sequence[Optional[torch.Tensor]] = ()) -> bool:
-    """Enqueue fn() on the side stream after the current stream's queued work, for the caller
-    to overlap with its next launch and then join with wait_side().  Returns False (fn ran on
-    the current stream) when side streams are off."""
-    if not (_enabled["on"] and _enabled["side"]) or \
-            (torch.cuda.is_current_stream_capturing() and not _enabled["capture"]):
-        fn()
-        return False
-    main = torch.cuda.current_stream()
-    dev = main.device.index if main.device.index is not None else torch.cuda.current_device()
-    side = _side.get(dev)
-    if side is None:
-        side = _side[dev] = torch.cuda.Stream(device=main.device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        fn()
-    for t in reads:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            t.record_stream(side)
-    return True
+# at import, so that a run that asks for the removed mode fails before it measures anything
+if os.environ.get("JMT_SIDE_STREAM", "0") == "1":
+    raise ValueError(_SIDE_REMOVED)

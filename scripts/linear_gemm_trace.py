@@ -40,7 +40,7 @@ FROZEN = ("mm_transformer.physiological_encoder.layers.0.feed_forward.0.bias",
           "mm_transformer.cross_attention_p.in_proj_weight",
           "mm_transformer.out_layer1.bias", "vregressor.3.weight")
 SWITCHES = ("JMT_WGRAD_DEFER", "JMT_WGRAD_MERGE", "JMT_FUSED_BGRAD", "JMT_WGRAD_GROUP",
-            "JMT_GROUPED", "JMT_FUSED_HEAD", "JMT_SIDE_STREAM")
+            "JMT_GROUPED", "JMT_FUSED_HEAD")
 
 
 def arms():
@@ -49,7 +49,7 @@ def arms():
     out += [(f"{k}={v}", *tf, {k: v}, False) for k, v in (
         ("JMT_WGRAD_DEFER", "0"), ("JMT_WGRAD_DEFER", "single"), ("JMT_WGRAD_MERGE", "0"),
         ("JMT_FUSED_BGRAD", "0"), ("JMT_WGRAD_GROUP", "0"), ("JMT_GROUPED", "0"),
-        ("JMT_FUSED_HEAD", "0"), ("JMT_SIDE_STREAM", "1"))]
+        ("JMT_FUSED_HEAD", "0"))]
     out += [("fp32", "TRANSFORMER", "FC", "fp32", {}, False),
             ("self_atten", "TRANSFORMER", "SELF_ATTEN", "bf16", {}, False),
             ("none_fc", "NONE", "FC", "bf16", {}, False),

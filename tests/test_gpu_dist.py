@@ -239,17 +239,14 @@ def test_two_rank_losses_unequal_shards_match_gathered_batch(kind):
         off += SIZES[rank]
 
 
-def _bucketed_worker(rank, world, port, q, jm="TRANSFORMER", side=True):
+def _bucketed_worker(rank, world, port, q, jm="TRANSFORMER"):
     """bench.py's N>1 step: FusedSGD's flat gradients in write-completion order and the
-    all-reduce issued bucket by bucket during the backward (jmt.dist.GradBucketer).  side=False
-    turns the weight-gradient side stream off (JMT_SIDE_STREAM=0, bench.py's probe steps)."""
+    all-reduce issued bucket by bucket during the backward (jmt.dist.GradBucketer)."""
     dist, jdist = _init(rank, world, port)
     try:
         from jmt import functional as JF
-        from jmt import streams
         from jmt.optim import FusedSGD
         from losses.loss import CCCLoss
-        streams.set_side_enabled(side)
         audio, video, lv, la = _inputs()
         lo, hi = jdist.shard_range(B, rank, world)
         m = _model(jm=jm).cuda()
@@ -282,13 +279,12 @@ def _bucketed_worker(rank, world, port, q, jm="TRANSFORMER", side=True):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("jm,side", [("TRANSFORMER", True), ("NONE", True),
-                                     ("TRANSFORMER", False)])
-def test_two_rank_overlapped_bucket_allreduce_matches_dataparallel_oracle(jm, side):
+@pytest.mark.parametrize("jm", ("TRANSFORMER", "NONE"))
+def test_two_rank_overlapped_bucket_allreduce_matches_dataparallel_oracle(jm):
     """the bucket gating must cover gradient writes on every stream —
-    the grouped w_JR model (side stream on / off) and the wo_JR model (c2), whose branch
-    backwards run on the run_parallel streams."""
-    out = sorted(_spawn_raw(_bucketed_worker, args=(jm, side)), key=lambda r: r[0])
+    the grouped w_JR model and the wo_JR model (c2), whose branch backwards run on the
+    run_parallel streams."""
+    out = sorted(_spawn_raw(_bucketed_worker, args=(jm,)), key=lambda r: r[0])
     ref_loss, ref_grads = _dp_oracle(jm)
     gmax = max(float(g.abs().max()) for g in ref_grads.values())
     (_, l0, g0, early0, nb), (_, l1, g1, _, _) = out

@@ -205,3 +205,27 @@ def test_attn_plan_table():
         od = Op(True, E)
         p = attn_plan(bf, 6, 1, T, T, E, q, k, v, od, od, q, k, v)
         assert (p.fwd, p.bwd, p.shared_q) == ("fused", "pds_dkdv", want)
+
+
+def test_set_side_enabled_off_is_the_only_mode():
+    """The weight-gradient side stream is gone; bench.py still calls its switch around the probe
+    steps: False is accepted and does nothing, True is an error."""
+    from jmt import streams
+    assert streams.set_side_enabled(False) is None
+    with pytest.raises(ValueError, match="side stream .* was removed"):
+        streams.set_side_enabled(True)
+
+
+def test_side_stream_in_the_environment_fails_the_import():
+    """JMT_SIDE_STREAM=1 is refused when jmt.streams is imported (a fresh process: the switch is
+    read once), so a benchmark run that asks for the removed mode ends before it measures."""
+    import subprocess
+    import sys
+    pkg = os.path.join(REPO_ROOT, "joint-multimodal-transformer-6th-abaw_amd")
+    env = dict(os.environ, JMT_SIDE_STREAM="1")
+    r = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, sys.argv[1]); "
+                        "import jmt.streams", pkg], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode != 0
+    assert "ValueError" in r.stderr and "side stream" in r.stderr and "was removed" in r.stderr, \
+        r.stderr[-2000:]
